@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the batched LOB + TD(lambda) hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch: every live book of every
 rank performs one Learner::_step equivalent (act -> performAction -> features ->
@@ -17,6 +17,9 @@ the environment.
 
 Prints ONE JSON line (rank 0).  `value` counts env-steps actually performed
 (device counter), inputs are generated in HBM before the timed region.
+`ms_per_step` is one of the K timed steps (with its share of the episode's
+lob_reset, see `value_is`).  `--dump-outputs DIR` writes what the last timed
+step left (dump_outputs).
 """
 import argparse
 import ctypes
@@ -146,6 +149,51 @@ def cpu_baseline():
                       % (g.n_events, episodes, steps)}
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: the whole dump stays below this
+DUMP_THETA_SAMPLE = 1 << 20    # weights kept per weight vector (memory_size 20 M: a fixed, seeded sample of this many)
+DUMP_SEED = 1994
+
+
+def sample_index(n, k, seed):
+    """Sorted indices of a fixed, seeded sample of k out of n; None when k >= n (keep all)."""
+    import numpy as np
+    if k >= n:
+        return None
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_outputs(eng, args, counters):
+    """--dump-outputs DIR: what the last timed step left for a caller of the learner, as DIR/<name>.npy (float32 / float64):
+    the weight vector(s) (with sum, sum |w|, sum w^2, non-zero count and max |w| of the whole vector under <name>_summary),
+    the books' last actions, rewards, TD errors, stepped flags and learner states, and the engine's counters.  A weight
+    vector longer than DUMP_THETA_SAMPLE, and a batch whose per-book arrays would not fit under DUMP_BYTES, are cut to a
+    fixed, seeded sample whose indices go to theta_index / book_index, so that two builds compare entry for entry."""
+    import numpy as np
+    out = {"counters": counters.astype(np.float64)}
+    for which, name in ((0, "theta"), (1, "theta_b"))[:2 if args.algo == "double_q" else 1]:
+        th = eng.theta(which)
+        out[name + "_summary"] = np.array([th.sum(), np.abs(th).sum(), np.square(th).sum(), np.count_nonzero(th), np.abs(th).max()],
+                                          np.float64)
+        idx = sample_index(th.size, DUMP_THETA_SAMPLE, DUMP_SEED)
+        out[name] = th if idx is None else th[idx]
+        if idx is not None:
+            out["theta_index"] = idx.astype(np.float64)
+        del th
+    per_book = {"last_actions": eng.last_actions().astype(np.float64), "last_rewards": eng.last_rewards(),
+                "last_td": eng.last_td(), "stepped": eng.stepped().astype(np.float64), "learner_state": eng.learner_state()}
+    row_bytes = sum(a.nbytes // a.shape[0] for a in per_book.values())
+    room = DUMP_BYTES - sum(a.nbytes for a in out.values()) - 64 * 1024      # (npy headers)
+    idx = sample_index(eng.B, max(1, room // (row_bytes + 8)), DUMP_SEED + 1)
+    if idx is not None:
+        out["book_index"] = idx.astype(np.float64)
+    for name, a in per_book.items():
+        out[name] = a if idx is None else a[idx]
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in out.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -170,6 +218,9 @@ def main():
     ap.add_argument("--epsilon", type=float, default=None, help="exploration rate of the timed leg (default: example.yaml's eps_init 0.8)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step left for a caller (theta, the books' last actions, "
+                         "rewards, TD errors and states) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (rank 0's shard)")
     args = ap.parse_args()
 
     from rl_markets_amd import launch
@@ -266,6 +317,8 @@ def main():
     elapsed = t1 - t0
     steps_done = int(c1[0] - c0[0])
     events_done = int(c1[1] - c0[1])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args, c1)          # (outside the timed region, before the legs below move the engine on)
 
     ktimes = {}
     if not args.no_kernel_timing:
