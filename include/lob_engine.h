@@ -313,6 +313,28 @@ int lob_stage_wait(lob_engine* e);
  * the phases stand in for its per-thread choice of episode file. */
 int lob_load_events_shared(lob_engine* e, const uint32_t* host_records, int64_t n_total, const int64_t* phase,
                            int32_t n_events);
+/* A library of recorded days resident in HBM, a day drawn per book and episode on the device (the reference's training loop:
+ * rs.sample() + env.LoadData before every episode, src/main.cpp:51-55, include/utilities/sampler.h:29-46; its test loop,
+ * src/main.cpp:215-239).  lob_load_days: `host_records` holds the n_days days back to back, day d is records
+ * day_first[d] .. day_first[d + 1] - 1 (day_first: int64[n_days + 1], day_first[0] = 0, at least 2 events per day); every
+ * day is validated and the library uploaded once.  It replaces any stream loaded before; lob_reset returns LOB_ESTATE
+ * until a selection has been made, and lob_stage_events returns LOB_ESTATE while the library is loaded (lob_load_events,
+ * lob_load_events_shared and lob_gen_events_device return the engine to their modes).  The track is sized by the longest
+ * day: a ring when that day is longer than the resident track.
+ * lob_days_select: every book draws its next day from days first_day .. first_day + n_days - 1.  LOB_DAYS_RANDOM:
+ * std::uniform_int_distribution<size_t>{0, n_days - 1} over each book's std::default_random_engine, seeded with
+ * (unsigned)(seed + global book id) at lob_load_days and persisting across draws.  LOB_DAYS_IN_ORDER: global book g plays
+ * first_day + g mod n_days.  lob_days_set: the day of every book from the host (int32[n_books]).  Both are enqueued on the
+ * engine's stream without waiting for it and take effect at the next lob_reset; a lob_reset without a new selection
+ * replays the same days.  LOB_EINVAL: a day out of range; LOB_ESTATE: no library, or between lob_td_step_begin and
+ * lob_td_step_end.  lob_get_days: the day each book is playing (int32[n_books]; LOB_ESTATE before the first lob_reset on
+ * the library). */
+#define LOB_DAYS_RANDOM 0
+#define LOB_DAYS_IN_ORDER 1
+int lob_load_days(lob_engine* e, const uint32_t* host_records, const int64_t* day_first, int32_t n_days);
+int lob_days_select(lob_engine* e, int32_t mode, int32_t first_day, int32_t n_days);
+int lob_days_set(lob_engine* e, const int32_t* host_day);
+int lob_get_days(lob_engine* e, int32_t* host_out);
 
 /* ---- environment interface (environment::Base, include/environment/base.h:117-151) */
 

@@ -32,6 +32,7 @@ QUOTE_TARGET, QUOTE_BOOK = 0, 1
 ALGO_SARSA, ALGO_QLAMBDA, ALGO_DOUBLE_Q, ALGO_R_LEARN, ALGO_ONLINE_R_LEARN, ALGO_DOUBLE_R_LEARN = 0, 1, 2, 3, 4, 5
 THETA_SHARED, THETA_PRIVATE = 0, 1
 POLICY_EPS_GREEDY, POLICY_BOLTZMANN = 0, 1
+DAYS_RANDOM, DAYS_IN_ORDER = 0, 1   # lob_days_select modes (LOB_DAYS_*)
 
 
 class _Strict(C.Structure):
@@ -151,6 +152,10 @@ def load():
         "lob_load_events": (C.c_int, [vp, vp, C.c_int32]),
         "lob_load_events_shared": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int32]),
         "lob_gen_events_device": (C.c_int, [vp, P(GenParams)]),
+        "lob_load_days": (C.c_int, [vp, vp, vp, C.c_int32]),
+        "lob_days_select": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32]),
+        "lob_days_set": (C.c_int, [vp, vp]),
+        "lob_get_days": (C.c_int, [vp, vp]),
         "lob_reset": (C.c_int, [vp]),
         "lob_step": (C.c_int, [vp, vp]),
         "lob_get_state": (C.c_int, [vp, vp]),

@@ -163,6 +163,21 @@ struct lob_engine {
     int stage_rc = LOB_OK;
     std::string stage_err;
     i64* phase_dev = nullptr;  // replayed stream: first record of every book's window
+    // Day library (lob_load_days): the days back to back in records_dev, their tables, and two sets of every book's
+    // (first record, length, day) -- the set the current episode plays and the one a selection writes for the next
+    bool lib = false;
+    int lib_days = 0;
+    i64* day_first_dev = nullptr;   // [lib_days] first record of each day
+    i32* day_len_dev = nullptr;     // [lib_days] its events
+    uint32_t* day_rng = nullptr;    // [B] each book's minstd_rand0 state (persists across draws)
+    i32* day_explicit = nullptr;    // [B] lob_days_set's days on the device
+    i32* day_explicit_host = nullptr;  // [B] pinned: the host side of that copy
+    hipEvent_t day_copied = nullptr;   // the copy out of day_explicit_host has been done
+    i64* lib_phase[2] = {nullptr, nullptr};
+    i32* lib_len[2] = {nullptr, nullptr};
+    i32* lib_day[2] = {nullptr, nullptr};
+    int lib_cur = -1;           // the set the current episode plays (-1: no episode on the library yet)
+    bool lib_pending = false;   // a selection waits for the next lob_reset (in set lib_cur ^ 1, or 0)
     Track* track_dev = nullptr;
     i32* actions_dev = nullptr;
     i64* cnt_sum = nullptr;     // the striped device counters added up (read_counters)
@@ -751,6 +766,23 @@ int lob_create(const lob_params* p, int32_t n_books, int32_t device, lob_engine*
     return LOB_OK;
 }
 
+// the day library's tables and per-book sets (set_records, lob_destroy)
+static void free_days(lob_engine* e) {
+    if (e->day_copied) hipEventSynchronize(e->day_copied);   // (the pinned buffer may still be read by a copy in flight)
+    for (void* p : {(void*)e->day_first_dev, (void*)e->day_len_dev, (void*)e->day_rng, (void*)e->day_explicit, (void*)e->lib_phase[0],
+                    (void*)e->lib_phase[1], (void*)e->lib_len[0], (void*)e->lib_len[1], (void*)e->lib_day[0], (void*)e->lib_day[1]})
+        if (p) hipFree(p);
+    if (e->day_explicit_host) hipHostFree(e->day_explicit_host);
+    if (e->day_copied) hipEventDestroy(e->day_copied);
+    e->day_first_dev = nullptr; e->day_len_dev = nullptr; e->day_rng = nullptr; e->day_explicit = nullptr; e->day_explicit_host = nullptr;
+    e->day_copied = nullptr;
+    for (int i = 0; i < 2; i++) { e->lib_phase[i] = nullptr; e->lib_len[i] = nullptr; e->lib_day[i] = nullptr; }
+    e->lib = false;
+    e->lib_days = 0;
+    e->lib_cur = -1;
+    e->lib_pending = false;
+}
+
 void lob_destroy(lob_engine* e) {
     if (!e) return;
     hipSetDevice(e->device);
@@ -772,6 +804,7 @@ void lob_destroy(lob_engine* e) {
     for (void* p : e->allocs) hipFree(p);
     if (e->records_dev) hipFree(e->records_dev);
     if (e->phase_dev) hipFree(e->phase_dev);
+    free_days(e);
     if (e->track_dev) hipFree(e->track_dev);
     if (e->dump_dev) hipFree(e->dump_dev);
     if (e->spx_gather) hipFree(e->spx_gather);
@@ -843,8 +876,10 @@ static int set_records(lob_engine* e, int32_t n_events, size_t n_rows) {
     e->S.records = nullptr;
     e->S.track = nullptr;
     e->S.rec_phase = nullptr;
+    e->S.rec_len = nullptr;
     e->S.n_events = 0;
     if (e->phase_dev) { hipFree(e->phase_dev); e->phase_dev = nullptr; }
+    free_days(e);
     const size_t bytes = n_rows * e->P.Wd * 4 + 256;  // (tail pad: drec_levels reads whole 16-byte quads past a short level array)
     // market track: resident (one entry per event) up to track_ring events per book, a ring of that many beyond
     e->chunked = n_events > e->track_ring;
@@ -1040,7 +1075,7 @@ static int stage_join(lob_engine* e) {
 }
 int lob_stage_events(lob_engine* e, const uint32_t* host_records, int32_t n_events) {
     if (!e || !host_records) { lob_set_error("lob_stage_events: bad argument"); return LOB_EINVAL; }
-    if (!e->have_events || e->S.rec_phase || n_events != e->S.n_events) {
+    if (!e->have_events || e->lib || e->S.rec_phase || n_events != e->S.n_events) {
         lob_set_error("lob_stage_events: needs a loaded per-book stream of the same length (lob_load_events first)");
         return LOB_ESTATE;
     }
@@ -1111,6 +1146,105 @@ int lob_load_events_shared(lob_engine* e, const uint32_t* host_records, int64_t 
     HIPCHK(hipStreamSynchronize(e->stream));
     e->have_events = true;
     e->S.rec_phase = e->phase_dev;
+    return LOB_OK;
+}
+
+int lob_load_days(lob_engine* e, const uint32_t* host_records, const int64_t* day_first, int32_t n_days) {
+    if (!e || !host_records || !day_first || n_days < 1) { lob_set_error("lob_load_days: bad argument"); return LOB_EINVAL; }
+    if (day_first[0] != 0) { lob_set_error("lob_load_days: day_first[0] must be 0"); return LOB_EINVAL; }
+    int32_t longest = 0;
+    std::vector<i32> len((size_t)n_days);
+    for (int d = 0; d < n_days; d++) {
+        const int64_t n = day_first[d + 1] - day_first[d];
+        if (n < 2 || day_first[d + 1] > INT32_MAX) {
+            lob_set_error("lob_load_days: day " + std::to_string(d) + " has fewer than 2 events, or day_first is not monotone / runs past 2^31 records");
+            return LOB_EINVAL;
+        }
+        len[d] = (i32)n;
+        longest = std::max(longest, (int32_t)n);
+    }
+    const int64_t n_total = day_first[n_days];
+    HIPCHK(hipSetDevice(e->device));
+    for (int d = 0; d < n_days; d++) {
+        const int rc = lob_validate_stream(host_records + (size_t)day_first[d] * e->P.W, e->P.D, e->P.T, 1, len[d]);
+        if (rc != LOB_OK) return rc;
+    }
+    // the track is sized by the longest day: a ring when that one is longer than the resident track
+    int rc = set_records(e, longest, (size_t)n_total);
+    if (rc != LOB_OK) return rc;
+    e->have_events = false;   // (until the library and its tables are in place)
+    rc = upload_records(e, host_records, (size_t)n_total);
+    if (rc != LOB_OK) return rc;
+    const size_t B = (size_t)e->B;
+    bool ok = hipMalloc((void**)&e->day_first_dev, (size_t)n_days * sizeof(i64)) == hipSuccess &&
+              hipMalloc((void**)&e->day_len_dev, (size_t)n_days * sizeof(i32)) == hipSuccess &&
+              hipMalloc((void**)&e->day_rng, B * sizeof(uint32_t)) == hipSuccess && hipMalloc((void**)&e->day_explicit, B * sizeof(i32)) == hipSuccess &&
+              hipHostMalloc((void**)&e->day_explicit_host, B * sizeof(i32), hipHostMallocDefault) == hipSuccess &&
+              hipEventCreateWithFlags(&e->day_copied, hipEventDisableTiming) == hipSuccess;
+    for (int i = 0; i < 2 && ok; i++)
+        ok = hipMalloc((void**)&e->lib_phase[i], B * sizeof(i64)) == hipSuccess && hipMalloc((void**)&e->lib_len[i], B * sizeof(i32)) == hipSuccess &&
+             hipMalloc((void**)&e->lib_day[i], B * sizeof(i32)) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); free_days(e); lob_set_error("hipMalloc(day library tables) failed"); return LOB_ENOMEM; }
+    // RandomSampler's std::default_random_engine rng(seed) (sampler.h:34-39): minstd_rand0 seeded with (unsigned)(seed + global book id)
+    std::vector<uint32_t> rng(B);
+    for (size_t b = 0; b < B; b++) {
+        const uint32_t s = (uint32_t)(e->P.seed + e->P.book_id_offset + (u64)b);
+        rng[b] = s % 2147483647u == 0 ? 1u : s % 2147483647u;
+    }
+    HIPCHK(hipMemcpyAsync(e->day_first_dev, day_first, (size_t)n_days * sizeof(i64), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->day_len_dev, len.data(), (size_t)n_days * sizeof(i32), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->day_rng, rng.data(), B * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->lib = true;
+    e->lib_days = n_days;
+    e->have_events = true;
+    return LOB_OK;
+}
+
+// a selection may be made with a library loaded and no learner step half done
+static int days_ready(lob_engine* e, const char* who) {
+    if (!e->lib) { lob_set_error(std::string(who) + ": no day library loaded (lob_load_days)"); return LOB_ESTATE; }
+    if (e->half_open) { lob_set_error(std::string(who) + ": a learner step is half done (lob_td_step_begin without lob_td_step_end)"); return LOB_ESTATE; }
+    return LOB_OK;
+}
+// a selection for the next episode: days_draw_kernel writes the set the current episode does not play
+static int days_draw(lob_engine* e, int mode, int first, int n) {
+    HIPCHK(hipSetDevice(e->device));
+    const int nx = e->lib_cur < 0 ? 0 : e->lib_cur ^ 1;
+    TimedLaunch t(e, "days_draw_kernel", nullptr, true);
+    lobk_days_draw(e->stream, e->B, e->P.book_id_offset, mode, first, n, e->day_explicit, e->day_rng, e->day_first_dev, e->day_len_dev, e->lib_phase[nx],
+                   e->lib_len[nx], e->lib_day[nx]);
+    HIPCHK(hipGetLastError());
+    e->lib_pending = true;
+    return LOB_OK;
+}
+int lob_days_select(lob_engine* e, int32_t mode, int32_t first_day, int32_t n_days) {
+    if (!e) return LOB_EINVAL;
+    { int rc = days_ready(e, "lob_days_select"); if (rc) return rc; }
+    if ((mode != LOB_DAYS_RANDOM && mode != LOB_DAYS_IN_ORDER) || first_day < 0 || n_days < 1 || (int64_t)first_day + n_days > e->lib_days) {
+        lob_set_error("lob_days_select: bad mode, or days " + std::to_string(first_day) + " + " + std::to_string(n_days) + " outside the library");
+        return LOB_EINVAL;
+    }
+    return days_draw(e, mode, first_day, n_days);
+}
+int lob_days_set(lob_engine* e, const int32_t* host_day) {
+    if (!e || !host_day) { lob_set_error("lob_days_set: bad argument"); return LOB_EINVAL; }
+    { int rc = days_ready(e, "lob_days_set"); if (rc) return rc; }
+    for (int b = 0; b < e->B; b++)
+        if (host_day[b] < 0 || host_day[b] >= e->lib_days) { lob_set_error("lob_days_set: day of book " + std::to_string(b) + " outside the library"); return LOB_EINVAL; }
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipEventSynchronize(e->day_copied));   // (the copy of the selection before has left the pinned buffer)
+    memcpy(e->day_explicit_host, host_day, (size_t)e->B * sizeof(i32));
+    HIPCHK(hipMemcpyAsync(e->day_explicit, e->day_explicit_host, (size_t)e->B * sizeof(i32), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipEventRecord(e->day_copied, e->stream));
+    return days_draw(e, LOB_DAYS_EXPLICIT, 0, 1);
+}
+int lob_get_days(lob_engine* e, int32_t* host_out) {
+    if (!e || !host_out) { lob_set_error("lob_get_days: bad argument"); return LOB_EINVAL; }
+    if (!e->lib || e->lib_cur < 0) { lob_set_error("lob_get_days: no episode on a day library yet (lob_load_days, a selection, lob_reset)"); return LOB_ESTATE; }
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipMemcpyAsync(host_out, e->lib_day[e->lib_cur], (size_t)e->B * sizeof(i32), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
     return LOB_OK;
 }
 
@@ -1188,9 +1322,16 @@ static void launch_env_fused(lob_engine* e, hipStream_t st, int par, int lpar, u
 int lob_reset(lob_engine* e) {
     if (!e) return LOB_EINVAL;
     if (!e->have_events) { lob_set_error("lob_reset: no event stream loaded"); return LOB_ESTATE; }
+    if (e->lib && e->lib_cur < 0 && !e->lib_pending) { lob_set_error("lob_reset: no days selected from the library (lob_days_select / lob_days_set)"); return LOB_ESTATE; }
     HIPCHK(hipSetDevice(e->device));
     { int rc = finalize_episode(e); if (rc) return rc; }   // (the window sums of the episode that ends: on the stream it ran on)
     { int rc = stage_adopt(e); if (rc) return rc; }        // a stream handed over meanwhile (lob_stage_events) is this episode's
+    if (e->lib_pending) {   // ... and so are the days selected meanwhile (lob_days_select / lob_days_set)
+        e->lib_cur = e->lib_cur < 0 ? 0 : e->lib_cur ^ 1;
+        e->lib_pending = false;
+        e->S.rec_phase = e->lib_phase[e->lib_cur];
+        e->S.rec_len = e->lib_len[e->lib_cur];
+    }
     { int rc = sync_state(e); if (rc) return rc; }
     // the memo table starts empty every episode (reset_kernel voids every book's slot)
     HIPCHK(hipMemsetAsync(e->S.mk_hash, 0xff, (size_t)e->S.mk_slots * 8, e->stream));

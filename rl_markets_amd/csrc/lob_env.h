@@ -136,6 +136,7 @@ struct EnvCtx {
         rows = s.records + first * (size_t)p.Wd;
     }
     __device__ EnvCtx(const DevParams& p, const DevState& s, int book, const TickLds* t, const uint32_t* rows_) : P(p), S(s), b(book), rows(rows_), tk(t) {}
+    __device__ i32 n_ev() const { return S.events_of(b); }
     __device__ void err(int bit) const { atomicOr(S.error_flag, bit); }
     __device__ const uint32_t* row(int i) const { return rows + (size_t)i * (size_t)P.Wd; }
     __device__ const Track& track(int k) const { return S.track[(size_t)b * (size_t)S.track_len + (size_t)(k & S.track_mask)]; }
@@ -1403,7 +1404,7 @@ __device__ inline int event_loop_fast(const EnvCtx& c, EnvR& e, StepAgg& g, TE& 
     EnvR h = e;  // registers from here to the end of the loop
     const FastKeys K{key4(h.a_opx), key4(h.b_opx)};
     c.mark(22);  // hot copy
-    const int last_row = c.S.n_events - 1;
+    const int last_row = c.n_ev() - 1;
     int st;
     while (true) {
         // the next event's entry and first row are requested a pass ahead (wasted on a step's last pass: skipping them there on a
@@ -1580,7 +1581,7 @@ struct PreRow {
 template <int TM>
 __device__ inline void pre_row_issue(const EnvCtx& c, int rec, PreRow<TM>& R) {
     const DevParams& P = c.P;
-    const int last = c.S.n_events - 1;
+    const int last = c.n_ev() - 1;
     const uint4* r4 = reinterpret_cast<const uint4*>(c.row(rec < last ? rec : last));  // (past the stream: the last row again, never looked at)
     const int d4 = drec_pad4(P.D) / 4;
     R.hdr = r4[0];
@@ -1592,7 +1593,7 @@ __device__ inline void pre_row_issue(const EnvCtx& c, int rec, PreRow<TM>& R) {
     for (int q = 0; q < (TM + 1) / 2; q++) R.tr[q] = 2 * q < P.T ? r4[1 + 4 * d4 + q] : make_uint4(0, 0, 0, 0);
 }
 __device__ inline i32 pre_row_time(const EnvCtx& c, int rec) {
-    const int last = c.S.n_events - 1;
+    const int last = c.n_ev() - 1;
     return (i32)c.row(rec < last ? rec : last)[LOB_REC_TIME];
 }
 // Intraday::UpdateBookProfiles as mk_update_book_profiles, the first row it applies taken from registers (`R0` = row m.cursor,
@@ -1604,7 +1605,7 @@ __device__ inline bool mk_update_book_profiles_pre(const EnvCtx& c, MarketR& m, 
     { f64 t = m.bp0; m.bp0 = m.lbp0; m.lbp0 = t; }
     bool regs = true;
     while (true) {
-        if (m.cursor + 1 >= c.S.n_events) return false;
+        if (m.cursor + 1 >= c.n_ev()) return false;
         const int rec = m.cursor;
         m.cursor++;
         m.records++;
@@ -1643,7 +1644,7 @@ __device__ inline bool mk_update_book_profiles(const EnvCtx& c, MarketR& m) {
     { f64 t = m.ap0; m.ap0 = m.lap0; m.lap0 = t; }
     { f64 t = m.bp0; m.bp0 = m.lbp0; m.lbp0 = t; }
     while (true) {
-        if (m.cursor + 1 >= c.S.n_events) return false;
+        if (m.cursor + 1 >= c.n_ev()) return false;
         const int rec = m.cursor;
         m.cursor++;
         m.records++;
@@ -1801,7 +1802,7 @@ __device__ inline void prepass_run(const EnvCtx& c, PrepState& st, BookMeta& M, 
         const int first = m.cursor;
 #if LOB_PRE_TOUCH
         {
-            const int last = c.S.n_events - 1;
+            const int last = c.n_ev() - 1;
             const uint32_t* r2 = c.row(first + 2 < last ? first + 2 : last);
             const int wl = P.Wd - 1;
             nt[0] = r2[0]; nt[1] = r2[16 < wl ? 16 : wl]; nt[2] = r2[32 < wl ? 32 : wl]; nt[3] = r2[wl];
@@ -1813,7 +1814,7 @@ __device__ inline void prepass_run(const EnvCtx& c, PrepState& st, BookMeta& M, 
         pre_row_issue<TM>(c, first + 1, R1);
         t2 = pre_row_time(c, first + 2);
 #endif
-        if (first < c.S.n_events && (R0.hdr.y & LOB_EVT_FLAG_TAS_DRY)) {
+        if (first < c.n_ev() && (R0.hdr.y & LOB_EVT_FLAG_TAS_DRY)) {
             // the time-and-sales stream has run dry (Streamer::LoadUntil fails, streamer.cpp:61-85): NextState returns
             // false before it touches the books -- out of data with nothing of this event applied (ex_first < 0)
             M.ex_first = -1; M.ex_cur = m.rec_cur; M.ex_last = m.rec_last; M.ex_time = m.time_ms; M.ex_records = 0;
@@ -2032,14 +2033,14 @@ __device__ inline void prepass_books_role(const DevParams* Pp, const DevState* S
                 const int first = m.cursor;
                 {   // the row two events ahead is touched (it is in L2 when its turn comes; its first word is the time the event
                     // before it compares with); the other wave of the SIMD runs while this one waits for its own row
-                    const int last = c.S.n_events - 1;
+                    const int last = c.n_ev() - 1;
                     const uint32_t* r2 = c.row(first + 2 < last ? first + 2 : last);
                     const int wl = P.Wd - 1;
                     nt[0] = r2[0]; nt[1] = r2[16 < wl ? 16 : wl]; nt[2] = r2[32 < wl ? 32 : wl]; nt[3] = r2[wl];
                 }
                 pre_row_issue<TM>(c, first, R0);
                 if (!piped) t1 = pre_row_time(c, first + 1);
-                if (first < c.S.n_events && (R0.hdr.y & LOB_EVT_FLAG_TAS_DRY)) {
+                if (first < c.n_ev() && (R0.hdr.y & LOB_EVT_FLAG_TAS_DRY)) {
                     M.ex_first = -1; M.ex_cur = m.rec_cur; M.ex_last = m.rec_last; M.ex_time = m.time_ms; M.ex_records = 0;
                     M.complete = 1;
                     break;

@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(64, EnvStepOcc<LANES>::waves) env_step_kernel(
     RowFull cur, first;
     row_full_load(c, rc0, cur);
     {
-        const int last_row = S.n_events - 1;
+        const int last_row = S.events_of(b) - 1;
         row_full_load(c, rc0 + 1 < last_row ? rc0 + 1 : last_row, first);
     }
     rm_prep(S.pnl_ups, B, b, wu);
@@ -464,7 +464,7 @@ __global__ void __launch_bounds__(64) env_step16_kernel(const DevParams* __restr
     cur.pending = first.pending = false;
     row_full_load(c, rc0, cur);
     {
-        const int last_row = S.n_events - 1;
+        const int last_row = S.events_of(b) - 1;
         row_full_load(c, rc0 + 1 < last_row ? rc0 + 1 : last_row, first);
     }
     rm_prep(S.pnl_ups, B, b, wu);

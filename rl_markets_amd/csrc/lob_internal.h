@@ -9,6 +9,8 @@
 #include "../../include/lob_engine.h"
 #include "lob_stream.h"
 
+#define LOB_DAYS_EXPLICIT 2   /* days_draw_kernel's third mode: the days of lob_days_set (LOB_DAYS_RANDOM / LOB_DAYS_IN_ORDER: lob_engine.h) */
+
 void lob_set_error(const std::string& s);
 
 // Tick maths shared by host (lob_to_ticks...) and device (state extraction,

@@ -125,6 +125,37 @@ __global__ void repack_kernel(const uint32_t* __restrict__ src, int D, int T, si
         *reinterpret_cast<uint4*>(dst + i * Wd + k) = make_uint4(drec[k], drec[k + 1], drec[k + 2], drec[k + 3]);
 }
 #endif
+#if LOB_IN_PREPASS
+// Day library (lob_load_days): the day every book plays next, one lane per book.  Random mode is the reference's
+// RandomSampler::sample() (include/utilities/sampler.h:29-46) restated: each book's std::default_random_engine (minstd_rand0,
+// x <- 16807 x mod 2^31 - 1, `rng`, seeded with seed + global book id by the host and persisting across draws) feeds
+// std::uniform_int_distribution<size_t>{0, n - 1} in libstdc++'s downscaling form -- the engine's range 2147483645 is not
+// 2^32 - 1, so scaling = range / n, redraw while x - 1 >= n * scaling, result (x - 1) / scaling.  In-order mode: global
+// book g plays first + g mod n (the test loop, src/main.cpp:215-239).  Explicit mode: `explicit_day` from the host.
+__global__ void days_draw_kernel(int B, u64 first_book, int mode, int first, int n, const i32* __restrict__ explicit_day, uint32_t* rng,
+                                 const i64* __restrict__ day_first, const i32* __restrict__ day_len, i64* rec_phase, i32* rec_len, i32* day) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int d;
+    if (mode == LOB_DAYS_RANDOM) {
+        const u64 range = 2147483645ull, scaling = range / (u64)n, past = (u64)n * scaling;
+        u64 x = rng[b], r;
+        do {
+            x = x * 16807ull % 2147483647ull;
+            r = x - 1;
+        } while (r >= past);
+        rng[b] = (uint32_t)x;
+        d = first + (int)(r / scaling);
+    } else if (mode == LOB_DAYS_IN_ORDER) {
+        d = first + (int)((first_book + (u64)b) % (u64)n);
+    } else {
+        d = explicit_day[b];
+    }
+    day[b] = d;
+    rec_phase[b] = day_first[d];
+    rec_len[b] = day_len[d];
+}
+#endif
 
 // ---------------------------------------------------------------------------
 // Base::Initialise + Intraday::Initialise (base.cpp:123-135, intraday.cpp:103-138)
@@ -200,7 +231,7 @@ __global__ void __launch_bounds__(RB) reset_kernel(const DevParams* __restrict__
         e.pf = M.rec_cur0;
         e.rec_cur = M.ex_cur; e.rec_last = M.ex_last; e.time_ms = M.ex_time;
         e.mid = 0.0; e.mid_prev = 0.0;
-        e.events += (i64)(S.n_events > 0 ? S.n_events - 1 : 0);
+        { const i32 n = c.n_ev(); e.events += (i64)(n > 0 ? n - 1 : 0); }
         e.done = 2;
     }
     S.hdr[b].stepped = 0;
@@ -296,7 +327,7 @@ __global__ void __launch_bounds__(128, 2) reset2_kernel(const DevParams* __restr
         e.pf = M.rec_cur0;
         e.rec_cur = M.ex_cur; e.rec_last = M.ex_last; e.time_ms = M.ex_time;
         e.mid = 0.0; e.mid_prev = 0.0;
-        e.events += (i64)(S.n_events > 0 ? S.n_events - 1 : 0);
+        { const i32 n = c.n_ev(); e.events += (i64)(n > 0 ? n - 1 : 0); }
         e.done = 2;
     }
     S.hdr[b].stepped = 0;
@@ -462,7 +493,7 @@ __global__ void __launch_bounds__(LOB_ENV_BLOCK) env_kernel(const DevParams* __r
             RowFull cur;
             row_full_load(c, rc0, cur);
             RowFull first;
-            if (LOB_FAST_PASS && TM == 2) row_full_load(c, rc0 + 1 < S.n_events - 1 ? rc0 + 1 : S.n_events - 1, first);
+            if (LOB_FAST_PASS && TM == 2) { const int last_row = c.n_ev() - 1; row_full_load(c, rc0 + 1 < last_row ? rc0 + 1 : last_row, first); }
             EnvR& e = lds_env[threadIdx.x].e;
             env_load(S, b, e);
             c.mark(20);  // agent scalars in

@@ -36,6 +36,8 @@ void lobk_dump(hipStream_t st, const DevParams* Pd, const DevState& S, int first
 // ---- lob_tu_prepass.hip ----
 void lobk_gen_events(hipStream_t st, const lob_gen_params& g, int D, int T, u64 first_book, int B, uint32_t* out);
 void lobk_repack(hipStream_t st, const uint32_t* src, int D, int T, size_t n_records, uint32_t* dst);
+void lobk_days_draw(hipStream_t st, int B, u64 first_book, int mode, int first, int n, const i32* explicit_day, uint32_t* rng, const i64* day_first,
+                    const i32* day_len, i64* rec_phase, i32* rec_len, i32* day);
 // reset_kernel<lanes, TM> (`roles`: reset2_kernel, `lanes` 16 | 32: experiments)
 void lobk_reset(hipStream_t st, int lanes, bool t2, bool roles, const DevParams* Pd, const DevState& S);
 void lobk_prepass_extend(hipStream_t st, bool t2, bool roles, const DevParams* Pd, const DevState& S);

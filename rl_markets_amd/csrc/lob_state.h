@@ -243,6 +243,9 @@ struct DevState {
     i32 n_events;
     GP<const uint32_t> records;  // device layout: [B][n_events][Wd], or one replayed stream [n_total][Wd] when rec_phase is set
     GP<const i64> rec_phase;     // [B] first record of each book's n_events-long window (lob_load_events_shared), else null
+    GP<const i32> rec_len;       // [B] events in book b's stream (a day of the library, lob_load_days: n_events is the longest), else null
+    // the length of book b's stream: every device read of n_events goes through here
+    __device__ __forceinline__ i32 events_of(int b) const { return rec_len ? rec_len[b] : n_events; }
 
 #define X(t, n) GP<t> n;
     LOB_ENV_FIELDS(X)

@@ -1,4 +1,4 @@
-// Translation unit of the once-per-episode kernels (lob_launch.h): the synthetic generator and the record repacker, reset_kernel
+// Translation unit of the once-per-episode kernels (lob_launch.h): the synthetic generator, the record repacker, the day draw, reset_kernel
 // with the market pre-pass, its resumption for long streams, finalize_kernel.  gfx950 only; no CPU execution path.
 #define LOB_TU_SPLIT 1
 #define LOB_TU_PREPASS 1
@@ -12,6 +12,12 @@ void lobk_gen_events(hipStream_t st, const lob_gen_params& g, int D, int T, u64 
 }
 void lobk_repack(hipStream_t st, const uint32_t* src, int D, int T, size_t n_records, uint32_t* dst) {
     hipLaunchKernelGGL(repack_kernel, dim3((unsigned)((n_records + 255) / 256)), dim3(256), 0, st, src, D, T, n_records, dst);
+}
+
+void lobk_days_draw(hipStream_t st, int B, u64 first_book, int mode, int first, int n, const i32* explicit_day, uint32_t* rng, const i64* day_first,
+                    const i32* day_len, i64* rec_phase, i32* rec_len, i32* day) {
+    hipLaunchKernelGGL(days_draw_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, first_book, mode, first, n, explicit_day, rng, day_first, day_len,
+                       rec_phase, rec_len, day);
 }
 
 void lobk_reset(hipStream_t st, int lanes, bool t2, bool roles, const DevParams* Pd, const DevState& S) {

@@ -138,6 +138,33 @@ class Engine:
     def gen_events(self, gen):
         self._check(self.lib.lob_gen_events_device(self.h, C.byref(gen)))
 
+    # ---- day library (lob_load_days) ----
+    def load_days(self, days):
+        """A library of recorded days, each records[n][W] (or [1][n][W], as convert_csv gives), resident in HBM."""
+        days = [np.asarray(d, dtype=np.uint32).reshape(-1, np.asarray(d).shape[-1]) for d in days]
+        first = np.zeros(len(days) + 1, dtype=np.int64)
+        first[1:] = np.cumsum([d.shape[0] for d in days])
+        rec = np.ascontiguousarray(np.concatenate(days, axis=0))
+        self._check(self.lib.lob_load_days(self.h, _ptr(rec), _ptr(first), len(days)))
+        self.day_first = first
+
+    def days_select(self, mode, first, n):
+        """Every book draws its next day from days first .. first + n - 1 (abi.DAYS_RANDOM / abi.DAYS_IN_ORDER);
+        the next reset() plays it."""
+        self._check(self.lib.lob_days_select(self.h, int(mode), int(first), int(n)))
+
+    def days_set(self, days):
+        """The day of every book for the next reset()."""
+        d = np.ascontiguousarray(days, dtype=np.int32)
+        assert d.shape == (self.B,)
+        self._check(self.lib.lob_days_set(self.h, _ptr(d)))
+
+    def days(self):
+        """The day each book is playing."""
+        out = np.zeros(self.B, dtype=np.int32)
+        self._check(self.lib.lob_get_days(self.h, _ptr(out)))
+        return out
+
     # ---- environment ----
     def reset(self):
         self._check(self.lib.lob_reset(self.h))

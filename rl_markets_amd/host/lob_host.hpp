@@ -23,6 +23,11 @@
 #ifndef LOB_HOST_HPP
 #define LOB_HOST_HPP
 
+#include <glob.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -265,6 +270,19 @@ public:
     // episode): returns at once, the Initialise() that follows adopts the stream; `records` must stay valid until then
     void StageData(const uint32_t* records, int n_events) { check(lob_stage_events(e_, records, n_events), "StageData"); }
     void StageWait() { check(lob_stage_wait(e_), "StageData"); }
+    // A directory of recorded days (src/main.cpp:51-55, 89-126): every day converted once and uploaded once as a day library
+    // (day d = records day_first[d] .. day_first[d + 1] - 1); SelectDays before an episode = every thread's rs.sample() +
+    // env.LoadData (LOB_DAYS_RANDOM), or the test loop over the held-out days (LOB_DAYS_IN_ORDER), drawn per book on the device
+    void LoadDays(const uint32_t* records, const std::vector<int64_t>& day_first) {
+        check(lob_load_days(e_, records, day_first.data(), (int32_t)day_first.size() - 1), "LoadDays");
+        invalidate();
+    }
+    void SelectDays(int mode, int first, int n) { check(lob_days_select(e_, mode, first, n), "SelectDays"); }
+    std::vector<int32_t> Days() {
+        std::vector<int32_t> d(B_);
+        check(lob_get_days(e_, d.data()), "Days");
+        return d;
+    }
 
     bool Initialise() {  // false = no data for at least one book (base.h:122)
         check(lob_reset(e_), "Initialise");
@@ -334,6 +352,35 @@ public:
 
 // ---------------------------------------------------------------------------
 // rl::Agent-shaped object: theta lives on the GPU inside the engine.
+// get_file_sample (include/utilities/files.h:39-76): (symbol, depth csv, time-and-sales csv) of every <md_dir>/<symbol>/*.csv in
+// glob order whose time-and-sales twin exists.  The twin's path is made with the reference's own string arithmetic: md_dir
+// replaced by tas_dir, then the two characters after the first "md_" of the ORIGINAL path's offset replaced by "tas" (so
+// "data/md/X/md_1.csv" -> "data/tas/X/tas_1.csv").
+inline std::vector<std::array<std::string, 3>> get_file_sample(const std::string& md_dir, const std::string& tas_dir,
+                                                               const std::vector<std::string>& symbols) {
+    auto exists = [](const std::string& path) { struct stat info; return stat(path.c_str(), &info) == 0; };
+    std::vector<std::array<std::string, 3>> all;
+    for (const std::string& s : symbols) {
+        const std::string md_s = md_dir + "/" + s, tas_s = tas_dir + "/" + s;
+        if (!exists(md_s)) throw std::runtime_error("No such directory: " + md_s);
+        if (!exists(tas_s)) throw std::runtime_error("No such directory: " + tas_s);
+        glob_t g;
+        std::vector<std::string> files;
+        if (glob((md_s + "/*.csv").c_str(), GLOB_TILDE, nullptr, &g) == 0)
+            for (size_t i = 0; i < g.gl_pathc; i++) files.push_back(g.gl_pathv[i]);
+        globfree(&g);
+        for (const std::string& f : files) {
+            std::string tf = f;
+            tf.replace(0, md_dir.size(), tas_dir);
+            const size_t loc = f.find("md_");
+            if (loc == std::string::npos) throw std::runtime_error("Unexpected file name: " + f);
+            tf.replace(loc + 1, 2, "tas");
+            if (access(tf.c_str(), F_OK) != -1) all.push_back({s, f, tf});
+        }
+    }
+    return all;
+}
+
 class Agent {
     BatchedIntraday& env_;
     double alpha_start_, alpha_floor_, omega_;

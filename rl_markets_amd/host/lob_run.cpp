@@ -10,14 +10,19 @@
 //            reference's N training threads on one shared Agent (src/main.cpp:196-206)
 //           [--md depth.csv --tas trades.csv | --lobster orderbook.csv message.csv LEVELS]   (a recorded day, replayed
 //            by every book from evenly spread starting records; default: synthetic streams)
+//           [--md-dir D --tas-dir D]   (or data.md_dir / data.tas_dir: the reference's directory of recorded days, src/main.cpp:89-239 --
+//            get_file_sample, the train / test split, a training day drawn per book before every episode, then one greedy
+//            evaluation over the held-out days with a row per day)
 #include <signal.h>
 #include <sys/wait.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <random>
 
 #include "lob_host.hpp"
 
@@ -72,8 +77,110 @@ int main(int argc, char** argv) {
     return rc;
 }
 
+// The reference's directory of recorded days (src/main.cpp:89-126): the (symbol, md, tas) pairs of get_file_sample, split into
+// a training and a test set, converted and uploaded once as the engine's day library -- the training days first, then the
+// held-out ones (none of their own when evaluation.use_train_sample replays the training days).
+struct DaySplit {
+    std::vector<std::array<std::string, 3>> files;   // in library order
+    int n_train = 0, test_first = 0, n_test = 0;
+    std::vector<uint32_t> records;                  // the converted days back to back, day i = records first[i] .. first[i + 1] - 1
+    std::vector<int64_t> first{0};
+};
+static DaySplit load_day_library(const lob::Config& c, const lob_params& p, const std::string& md_dir, const std::string& tas_dir,
+                                 lob::BatchedIntraday& env) {
+    if (md_dir.empty() || tas_dir.empty()) throw std::runtime_error("data.md_dir and data.tas_dir (--md-dir, --tas-dir) go together");
+    if (p.depth != 5) throw std::invalid_argument("the reference's CSV days have 5 levels (--depth 5)");
+    const std::vector<std::string> symbols = c.has("data.symbols") ? c.list("data.symbols") : std::vector<std::string>{"HSBA.L"};
+    // one venue per engine: the tick table is a parameter of the whole batch
+    lob_market m0, m;
+    for (size_t i = 0; i < symbols.size(); i++) {
+        lob::check(lob_market_preset(symbols[i].c_str(), i ? &m : &m0), "Market::make_market");
+        if (i && memcmp(&m, &m0, sizeof m) != 0)
+            throw std::invalid_argument("symbols " + symbols[0] + " and " + symbols[i] + " trade on different venues: one venue per engine");
+    }
+    auto files = lob::get_file_sample(md_dir, tas_dir, symbols);
+    const unsigned seed = (unsigned)p.seed;
+    const bool eval_from_train = c.boolean("evaluation.use_train_sample", false);
+    long n_eval = c.integer("evaluation.n_samples", -1);
+    long n_train_samples = c.integer("training.n_samples", -1);
+    std::vector<std::array<std::string, 3>> train, test;
+    if (eval_from_train) {
+        std::shuffle(files.begin(), files.end(), std::default_random_engine(seed));
+        train = files;
+    } else {
+        if (n_eval == -1) n_eval = (long)files.size();
+        if (n_eval < 0 || n_eval > (long)files.size()) throw std::runtime_error("evaluation.n_samples exceeds the days found");
+        const long pivot = (long)files.size() - n_eval;
+        train.assign(files.begin(), files.begin() + pivot);
+        test.assign(files.begin() + pivot, files.end());
+    }
+    if (n_train_samples < 0) n_train_samples = (long)train.size();
+    else if ((size_t)n_train_samples > train.size()) throw std::runtime_error("Insufficient training samples.");
+    train.erase(train.begin(), train.begin() + (train.size() - n_train_samples));
+    if (train.empty()) throw std::runtime_error("no training days in " + md_dir);
+    DaySplit d;
+    d.files = train;
+    d.n_train = (int)train.size();
+    if (eval_from_train) {
+        d.test_first = 0;
+        d.n_test = n_eval < 0 ? 0 : (int)std::min<long>(n_eval, d.n_train);
+    } else {
+        d.test_first = d.n_train;
+        d.n_test = (int)test.size();
+        d.files.insert(d.files.end(), test.begin(), test.end());
+    }
+    const size_t W = (size_t)lob_record_words(p.depth, p.max_trades);
+    for (const auto& f : d.files) {
+        uint32_t* rec = nullptr;
+        int32_t n = 0;
+        lob::check(lob_convert_csv(f[1].c_str(), f[2].c_str(), p.max_trades, &rec, &n), "LoadData");
+        d.records.insert(d.records.end(), rec, rec + (size_t)n * W);
+        lob_free(rec);
+        d.first.push_back(d.first.back() + n);
+    }
+    env.LoadDays(d.records.data(), d.first);
+    fprintf(stderr, "[-] %zu days: training on %d, testing on %d\n", d.files.size(), d.n_train, d.n_test);
+    return d;
+}
+
+// The final testing phase (src/main.cpp:211-239): GoGreedy(), then every test day in a FRESH environment (main.cpp:214) with the
+// trained weights -- here one lock-step Backtester episode per n_books test days, book i of a round playing test day i
+// (LOB_DAYS_IN_ORDER) -- and the reference's five figures per day.  Private theta: every test book gets book 0's weights.
+static void evaluate_days(const lob::Config& c, const lob_params& p, const DaySplit& d, lob::BatchedIntraday& trained) {
+    const int B = std::min(d.n_test, trained.n_books());
+    lob_params q = p;
+    q.book_id_offset = 0;
+    lob::BatchedIntraday env(q, B, 0);
+    env.LoadDays(d.records.data(), d.first);
+    lob::Agent agent(env, c);
+    {   // the trained agent's weights (theta, then theta_b of the double agents)
+        const bool priv = p.theta_mode == LOB_THETA_PRIVATE, dq = p.algo == LOB_ALGO_DOUBLE_Q;
+        const int nt_src = priv ? trained.n_books() : 1, nt = priv ? B : 1;
+        std::vector<double> th((size_t)p.memory_size);
+        for (int vec = 0; vec < (dq ? 2 : 1); vec++) {
+            lob::check(lob_theta_get(trained.handle(), vec * nt_src, th.data(), (int64_t)th.size()), "GoGreedy");
+            for (int t = 0; t < nt; t++) lob::check(lob_theta_set(env.handle(), vec * nt + t, th.data(), (int64_t)th.size()), "GoGreedy");
+        }
+    }
+    agent.GoGreedy();
+    printf("test,episode,symbol,file,reward,rho,pnl,n_tr,ppt\n");
+    for (int r0 = 0; r0 < d.n_test; r0 += B) {
+        const int n = std::min(B, d.n_test - r0);
+        env.SelectDays(LOB_DAYS_IN_ORDER, d.test_first + r0, n);
+        lob::Backtester bt(env);
+        if (!bt.RunEpisode(&agent)) { fprintf(stderr, "[!] no data in test days %d..%d\n", r0 + 1, r0 + n); continue; }
+        for (int i = 0; i < n; i++) {
+            const auto& f = d.files[d.test_first + r0 + i];
+            const double pnl = env.getEpisodePnL(i);
+            const int ntr = env.getTotalTransactions(i);
+            printf("test,%d,%s,%s,%.10g,%.10g,%.10g,%d,%.10g\n", r0 + i + 1, f[0].c_str(), f[1].c_str(), env.getEpisodeReward(i),
+                   env.getMeanEpisodeReward(i), pnl, ntr, pnl / ntr);
+        }
+    }
+}
+
 static int run(int argc, char** argv, int rank, int world, const std::string& rdzv) {
-    std::string cfg_path, algo, theta_out, profit_log, stats_out, md, tas, lob_ob, lob_msg;
+    std::string cfg_path, algo, theta_out, profit_log, stats_out, md, tas, lob_ob, lob_msg, md_dir, tas_dir;
     int lob_levels = 0;
     int books = 1, episodes = -1, events = 2112, depth = 5, sync_every = 64;
     for (int i = 1; i < argc; i++) {
@@ -90,6 +197,8 @@ static int run(int argc, char** argv, int rank, int world, const std::string& rd
         else if (a == "--stats-out") stats_out = next();   // env.writeStats(output_dir + "test_stats.csv"), src/main.cpp:242
         else if (a == "--md") md = next();
         else if (a == "--tas") tas = next();
+        else if (a == "--md-dir") md_dir = next();
+        else if (a == "--tas-dir") tas_dir = next();
         else if (a == "--lobster") { lob_ob = next(); lob_msg = next(); lob_levels = atoi(next().c_str()); }
         else if (a == "--gpus") next();
         else if (a == "--sync-every") sync_every = atoi(next().c_str());
@@ -108,7 +217,12 @@ static int run(int argc, char** argv, int rank, int world, const std::string& rd
         lob::BatchedIntraday env(p, books, rank);
         lob_comm* comm = nullptr;
         if (!rdzv.empty()) lob::check(lob_comm_create_file(rdzv.c_str(), rank, world, rank, 300, &comm), "lob_comm_create_file");
-        if (!md.empty() || !lob_ob.empty()) {
+        if (md_dir.empty() && c.has("data.md_dir")) md_dir = c.str("data.md_dir");
+        if (tas_dir.empty() && c.has("data.tas_dir")) tas_dir = c.str("data.tas_dir");
+        DaySplit days;
+        if (!md_dir.empty() || !tas_dir.empty()) {
+            days = load_day_library(c, p, md_dir, tas_dir, env);
+        } else if (!md.empty() || !lob_ob.empty()) {
             // the reference's data files (Intraday::LoadData reads the CSV pair, intraday.cpp:141-150)
             uint32_t* rec = nullptr;
             int32_t n = 0;
@@ -132,16 +246,19 @@ static int run(int argc, char** argv, int rank, int world, const std::string& rd
         if (rank == 0) printf("episode,episode_id,reward,pnl,n_steps,epsilon\n");
         for (int ep = 0; ep < episodes; ep++) {
             auto t0 = std::chrono::steady_clock::now();
+            if (days.n_train > 0) env.SelectDays(LOB_DAYS_RANDOM, 0, days.n_train);   // rs.sample() + env.LoadData, src/main.cpp:53-55
             if (!learner.RunEpisode(&agent)) { fprintf(stderr, "[!] no data\n"); return 2; }
             double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             int64_t cnt[4];
             lob::check(lob_get_counters(env.handle(), cnt), "counters");
-            if (rank == 0) printf("%d,%s,%.10g,%.10g,%d,%.6g\n", ep + 1, env.getEpisodeId().c_str(), env.getEpisodeReward(0), env.getEpisodePnL(0),
+            const std::string ep_id = days.n_train > 0 ? days.files[env.Days()[0]][1] : env.getEpisodeId();
+            if (rank == 0) printf("%d,%s,%.10g,%.10g,%d,%.6g\n", ep + 1, ep_id.c_str(), env.getEpisodeReward(0), env.getEpisodePnL(0),
                    env.book(0).total_ticks, agent.epsilon_);
             fprintf(stderr, "[rank %d/%d] episode %d: %lld env-steps over %d books in %.3f s\n", rank, world, ep + 1, (long long)cnt[0], books, sec);
         }
         if (!theta_out.empty() && rank == 0) agent.write_theta(theta_out);  // replicas agree after the last exchange
         if (comm) { lob_comm_barrier(comm); lob_comm_destroy(comm); comm = nullptr; }
+        if (days.n_test > 0 && rank == 0) evaluate_days(c, p, days, env);
         if (!profit_log.empty() && rank == 0) {
             // src/main.cpp:217-239: GoGreedy() then one Backtester episode with profit logging (book 0)
             agent.GoGreedy();
