@@ -71,6 +71,7 @@ struct lob_engine {
     bool no_hint = false;       // (experiment: learn_q_rest_kernel without its report to the host)
     bool exp_learn_first = false;  // (experiment LOB_SARSA_LEARN_FIRST=1: DevParams::exp_learn_first)
     long long flow[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // lob_debug_flow: learner steps by the shape of their update / action selection (see there)
+    long long hint_reads = 0, hint_misses = 0;  // lob_debug_hint: learner steps that read a hint word / found it still unwritten after the spin limit
     bool acc_fuse = true;       // Q(lambda), the pair kernel + the lane-per-generation trace kernel: updates added to their slots there, accumulate_kernel over a list (LOB_ACC_FUSE=0: over every book; A/B switch)
     bool acc_batches_set = false;
     int acc_batches = LOB_ACB_K;  // accumulate_block_kernel: batches of 1 024 books per block (LOB_ACC_BATCHES=1|2|4|8; A/B switch)
@@ -1541,8 +1542,12 @@ static int run_steps(lob_engine* e, int32_t n_steps, int mode, int half = 0) {
                 u64 w = *(volatile u64*)(e->rest_hint + hs);
                 for (int spin = 0; (uint32_t)(w >> 32) != e->hint_tags[hs] && spin < (1 << 16); spin++) w = *(volatile u64*)(e->rest_hint + hs);
                 // The count only chooses between two correct paths: a word that has still not arrived (a loaded host, a slow link)
-                // is no reason to abort training -- this step goes by "no book handed back" 
-                e->hint_now = (uint32_t)(w >> 32) == e->hint_tags[hs] ? (int)(uint32_t)w : 0;
+                // is no reason to abort training -- this step goes by "no book handed back" (ADVICE r5), and is counted
+                // (lob_debug_hint: a test that asserts which path ran must know that the hint decided it)
+                const bool arrived = (uint32_t)(w >> 32) == e->hint_tags[hs];
+                e->hint_now = arrived ? (int)(uint32_t)w : 0;
+                e->hint_reads++;
+                if (!arrived) e->hint_misses++;
             }
         }
         bool rest_pending = false;
@@ -2341,6 +2346,16 @@ extern "C" int lob_debug_fastpath(lob_engine* e, int64_t* out, int32_t n_out) {
 extern "C" int lob_debug_flow(lob_engine* e, int64_t out[8]) {
     if (!e || !out) return LOB_EINVAL;
     for (int i = 0; i < 8; i++) out[i] = e->flow[i];
+    return LOB_OK;
+}
+
+// Diagnostics (not part of include/lob_engine.h): learner steps since lob_create that [0] read the learn kernels' hand-back count
+// (the hint of LOB_HINT_LAG steps ago), [1] of those, steps whose hint word had not arrived within the spin limit and that went by
+// a count of 0 instead -- the path such a step took was chosen by the host's timing, not by the run.
+extern "C" int lob_debug_hint(lob_engine* e, int64_t out[2]) {
+    if (!e || !out) return LOB_EINVAL;
+    out[0] = e->hint_reads;
+    out[1] = e->hint_misses;
     return LOB_OK;
 }
 

@@ -314,6 +314,15 @@ class Engine:
                 "act_inline_general": int(c[4]), "act_work_list_dense": int(c[5]), "act_work_list_other": int(c[6]),
                 "dense_sums": int(c[7])}
 
+    def hint_stats(self):
+        """lob_debug_hint (a diagnostic export): learner steps that read the learn kernels' hand-back count, and of those the steps
+        whose count had not arrived in time and that went by 0 instead (their act / update path was chosen by the host's timing)."""
+        c = np.zeros(2, np.int64)
+        fn = self.lib.lob_debug_hint
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p]
+        self._check(fn(self.h, _ptr(c)))
+        return {"hint_read": int(c[0]), "hint_missed": int(c[1])}
+
     def deferred_generations(self):
         """lob_debug_deferred (a diagnostic export): generations without a combine slot that trace_rest_kernel left to apply_kernel so far."""
         c = np.zeros(1, np.int64)

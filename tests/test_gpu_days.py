@@ -19,13 +19,13 @@ pytestmark = pytest.mark.gpu
 DEPTH, TRADES = 5, 2
 
 
-def make_days(lengths, first_id=1000):
+def make_days(lengths, first_id=1000, depth=DEPTH):
     """Synthetic days of the given lengths, each its own generator book id (different content)."""
     out = []
     for i, n in enumerate(lengths):
         g = engine.default_gen_params()
         g.n_events = int(n)
-        out.append(engine.gen_stream_host(g, DEPTH, TRADES, first_id + i, 1)[0])
+        out.append(engine.gen_stream_host(g, depth, TRADES, first_id + i, 1)[0])
     return out
 
 

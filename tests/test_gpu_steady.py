@@ -286,17 +286,22 @@ def test_preloaded_theta_with_a_million_written_weights():
     orc.close()
 
 
-@pytest.mark.parametrize("forced", [False, True], ids=["by_hint", "forced"])
+@pytest.mark.parametrize("forced", [False, True, "never"], ids=["by_hint", "forced", "never"])
 def test_dense_theta_from_random_init_takes_the_work_list_act_path(monkeypatch, forced):
     """learning.random_init: true (src/rl/agent.cpp:37-39) at scale -- EVERY weight 2u - 1 from the agent's mt19937_64, so every
     tile lies on a written weight, no hit list fits a record and every book takes two full evaluations per step.  32 768 books,
     M = 20 M, against the oracle, and the flow counters ASSERT which act path the compared steps took: `by_hint` -- the first
     steps in full inside the env kernel (act_book), then, once the learn kernels' hand-back count of 16 steps ago says "most
     books" (lob_engine.hip LOB_HINT_LAG), through the work list to the wave-per-book act kernel + env_kernel<64, 2, 2> and the
-    accumulate pass over every book; `forced` (LOB_MOSTLY_GENERAL=1) -- that path from the second step on."""
-    if forced:
+    accumulate pass over every book; `forced` (LOB_MOSTLY_GENERAL=1) -- that path from the second step on; `never`
+    (LOB_MOSTLY_GENERAL=0) -- the act path a step takes when its hint word has not arrived (it goes by a count of 0), on the
+    theta where the hint chooses the other one.  (Only the act path: the hint still decides whether the update is fused, so
+    `hint_missed == 0` -- Engine.hint_stats -- is what says the update path was the run's own.)"""
+    if forced == "never":
+        monkeypatch.setenv("LOB_MOSTLY_GENERAL", "0")
+    elif forced:
         monkeypatch.setenv("LOB_MOSTLY_GENERAL", "1")
-    B, n_steps = 32768, 12 if forced else 22
+    B, n_steps = 32768, 12 if forced is True else 22
     p, eng, orc = make(B, abi.ALGO_QLAMBDA, n_events=200, random_init=1)
     th0 = eng.theta()
     np.testing.assert_array_equal(th0, orc.theta())          # the same 20 M draws, bit for bit
@@ -305,11 +310,18 @@ def test_dense_theta_from_random_init_takes_the_work_list_act_path(monkeypatch, 
     for step in range(n_steps):
         eng.td_step(1); orc.td_step(1)
         if step < 2 or step % 5 == 4 or step >= n_steps - 3:
-            compare_learner_step(eng, orc, "dense theta (%s), step %d" % ("forced" if forced else "by hint", step), exact=False, rtol=1e-9)
+            compare_learner_step(eng, orc, "dense theta (%s), step %d" % ({False: "by hint", True: "forced"}.get(forced, forced), step), exact=False, rtol=1e-9)
     flow, ps = eng.flow_stats(), eng.path_stats()
-    print("dense theta:", flow, "hit-list books %d, in-kernel full evaluations %d, handed back %d" % (ps[1], ps[6], ps[7]))
+    print("dense theta:", flow, "hit-list books %d, in-kernel full evaluations %d, handed back %d" % (ps[1], ps[6], ps[7]), eng.hint_stats())
     assert ps[1] == 0 and ps[7] >= (n_steps - 1) * B          # no book ever replays a list; the learn kernel hands every book back
-    if forced:
+    if forced == "never":
+        # launch_env_fused (lob_engine.hip): the first step acts without hit lists (act_fast_kernel, not counted), the first step on
+        # lists goes through the work list for that reason alone (act_work_list_other), every later one serves its list-less books
+        # inside the env kernel -- although from step 17 on the hand-back count says "most books"
+        assert flow["act_inline_general"] == n_steps - 2 and flow["act_work_list_other"] == 1 and flow["act_work_list_dense"] == 0, flow
+        hs = eng.hint_stats()
+        assert hs["hint_missed"] == 0 and hs["hint_read"] >= n_steps - 16, hs
+    elif forced:
         assert flow["act_work_list_dense"] == n_steps - 1 and flow["act_inline_general"] == 0, flow
     else:
         assert flow["act_inline_general"] >= 14 and flow["act_work_list_dense"] >= 4, flow
