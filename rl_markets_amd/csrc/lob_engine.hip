@@ -11,7 +11,9 @@
 #include <string.h>
 
 #include <algorithm>
+#include <climits>
 #include <condition_variable>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -46,41 +48,71 @@ struct KTimer {
     int64_t launches = 0;
 };
 
+// Runtime switches (INTEGRATION.md §6 says what each does), read once by read_switches at lob_create.  Honoured by every build:
+// the A/B switches of first-class paths that the parity tests force on or off at sizes that would not select them, the table sizes
+// the tests squeeze, the track ring, the upload's pieces and the exchange's first count.  The switches of variants measured and
+// lost, and of timing experiments, only by a -DLOB_EXPERIMENTS build (tools/exp_variants.sh; NOTES.md): read_switches leaves
+// them at their defaults otherwise.  (LOB_DENSE_EXCHANGE is lob_comm.cpp's.)
+struct Switches {
+    bool no_memo = false, no_carry = false, no_combine = false, light = true, force_fuse_act = false, t_light = true, no_fuse = false;
+    bool q_pair = true, dq_pair = true, trace_lanes_off = false, acc_fuse = true, rest_merge = true, acc_dense = true;
+    int q_lanes = -1, force_general = -1;  // -1: by batch size / by the learn kernels' hand-back count
+    int env_lanes = 0, env16_max = 4096;   // env_lanes 0: by batch size
+    int acc_batches = 0, acc_shift = -1;   // 0 / -1: by algorithm, batch size and epsilon
+    int cb_slots = 0, ow_slots = 0, amb_cap = 0, cbd_ids = 0;  // 0: by size
+    int track_ring = 4096, track_refill = 64;
+    long long upload_piece_recs = 0, spx_count = 0;  // 0: 64 MB pieces / by table size
+    bool upload_pinned = true;
+    // (-DLOB_EXPERIMENTS builds only)
+    bool fuse_act = true, inline_general = true, env_step = true, prepass_roles = false, sarsa_lanes_off = false, dq_fast_off = false;
+    bool rest_side = true, acc_block = true, exp_learn_first = false, no_hint = false;
+    int env_step_lanes = 64, reset_lanes = 64, n_groups = 1, acc_reps = 0, ts_lds = 0, ts_grid = 0;  // acc_reps 0: by path
+};
+
+// The kernel paths fixed for the engine's life, by plan_paths from the parameters, the batch, the CU count and the switches.
+// DevParams carries memo / combine / carry_verdicts / sarsa_lanes from here; run_steps takes every other fixed choice from here.
+struct EnginePlan {
+    int groups = 1;             // book groups of the step pipeline
+    bool combine = false, memo = false, carry_verdicts = false, sarsa_lanes = false;  // (DevParams)
+    bool q_lanes = false;       // Q(s', .) + TD error with lanes per book, else a wave per book (learn_q_fast_kernel)
+    bool q_pair = false;        // ... two per book (learn_q_pair_kernel), else one (learn_q_lane_kernel)
+    bool t_light = false;       // Q(lambda) / double Q: the light trace step for the books that keep no older generation
+    bool fuse = false;          // ... inside the lane learn kernel, else trace_light_kernel
+    bool fused_act_ok = false;  // the action selection may ride in the env kernel (fast-path learner steps on live hit lists)
+    bool env_step = false, half_waves = false, env16 = false;  // ... in env_step_kernel (else env_kernel<64, TM, 1>): 32 lanes / 16 lanes per book
+    bool inline_ok = false;     // ... which may serve the books without a hit list itself
+    int env_lanes = 64;         // books per env_kernel wave
+    bool acc_block_ok = false;  // the update may sum per block (StepPlan::acc_blocked), ...
+    bool dense_ids = false;     // ... by the slots' dense ids
+    bool acc_fuse_ok = false;   // updates may be added to their slots by the learn / trace kernels (StepPlan::acc_fused)
+    bool rest_side_ok = false;  // learn_q_rest_kernel may run on the second stream
+    bool learn_first = false;   // (experiment) SARSA(lambda)'s learn kernels in front of its trace kernels
+};
+
 struct lob_engine {
     int device = 0;
     int B = 0;
     lob_params params;
+    Switches sw;
+    EnginePlan plan;
     DevParams P;
     DevParams* P_dev = nullptr;  // device copy for the lane-per-book kernels
     DevState S;
     // The device-resident copy of S, at one address for the engine's lifetime (S.self): kernels that take the state by POINTER read
     // the fields they need where they need them, through the scalar cache -- 1 728 bytes of by-value kernel arguments are loaded at
     // the kernel's entry, live across all of it and cost env_step_kernel 104 spilled scalar registers + 160 vector registers parked
-    // in AGPRs (round 6).  Kept up by sync_state() before every launch sequence; the two words a step changes (cb_par,
-    // cb_dense_on) are never read through the pointer: they travel as scalar arguments.
+    // in AGPRs (round 6).  Kept up by sync_state() before every launch sequence, which uploads the two words a learner step
+    // changes (cb_par, cb_dense_on) as 0; the claims read them through the pointer (cb_claim_finish), so every learner step
+    // publishes them before its first claim (publish_step_words).
     DevState* S_dev = nullptr;
     DevState S_pushed;
     hipStream_t stream = nullptr;   // main stream (all API calls)
     hipStream_t stream2 = nullptr;  // second book group of the step pipeline
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_stagger = nullptr;
     hipEvent_t ev_rest_go = nullptr, ev_rest_done = nullptr;  // learn_q_rest_kernel on stream2 beside the trace kernels
-    bool rest_side = true;      // (LOB_REST_SIDE=0: on the main stream, as before; A/B switch)
-    bool rest_merge = true;     // the fused Q(lambda) / double Q flow: trace_rest_kernel (LOB_REST_MERGE=0: learn_q_rest_kernel + trace_fast_kernel<., 2> + accumulate_kernel over its list; A/B switch)
-    bool dq_pair = true;        // double Q(lambda): learn_q_pair_kernel<DOUBLE_Q> (LOB_DQ_PAIR=0: a lane per book, learn_q_lane_kernel; A/B switch)
-    int ts_lds = 0, ts_grid = 0; // (experiments: trace_lane_kernel<SARSA> with dynamic LDS / a persistent grid)
-    bool no_hint = false;       // (experiment: learn_q_rest_kernel without its report to the host)
-    bool exp_learn_first = false;  // (experiment LOB_SARSA_LEARN_FIRST=1: DevParams::exp_learn_first)
     long long flow[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // lob_debug_flow: learner steps by the shape of their update / action selection (see there)
     long long hint_reads = 0, hint_misses = 0;  // lob_debug_hint: learner steps that read a hint word / found it still unwritten after the spin limit
-    bool acc_fuse = true;       // Q(lambda), the pair kernel + the lane-per-generation trace kernel: updates added to their slots there, accumulate_kernel over a list (LOB_ACC_FUSE=0: over every book; A/B switch)
-    bool acc_batches_set = false;
-    int acc_batches = LOB_ACB_K;  // accumulate_block_kernel: batches of 1 024 books per block (LOB_ACC_BATCHES=1|2|4|8; A/B switch)
-    bool acc_block = true;      // SARSA(lambda): sums per block first (LOB_ACC_BLOCK=0: accumulate_kernel; A/B switch)
     bool dense_ever = false;    // the dense sums have been on at some step: slots may hold dense ids (apply_kernel frees them with their slots)
-    bool acc_dense = true;      // ... in a direct-indexed LDS array by the slots' dense ids, accumulate_dense_kernel (LOB_ACC_DENSE=0: accumulate_block_kernel's hash table; A/B switch)
-    int env_step_lanes = 64;    // books per wave of env_step_kernel (LOB_ENV_STEP_LANES=32: two half-full waves per SIMD; experiment)
-    int env16_max = 4096;       // largest batch that takes env_step16_kernel (16 lanes per book) instead of env_step_kernel (LOB_ENV16_MAX; 0: never)
-    bool prepass_roles = false; // the pre-pass on two waves per 64 books (reset2_kernel / prepass_extend2_kernel; LOB_PREPASS_ROLES=1): measured slower, opt-in
     // learn_q_rest_kernel reports its list's length (the books the lane learn kernels handed back) through host-mapped memory:
     // a ring of LOB_HINT_RING words, one per learner step, each with an event recorded behind the kernel that writes it.  The
     // step launched now reads the word of LOB_HINT_LAG steps ago after waiting for THAT event (long past, unless the host is
@@ -96,36 +128,20 @@ struct lob_engine {
     unsigned long long hint_serial = 0;  // launches of learn_q_rest_kernel since lob_create (the tag of a ring word)
     uint32_t hint_tags[LOB_HINT_RING] = {};
     int hint_now = 0;           // the hint this step goes by (run_steps)
-    int force_general = -1;     // LOB_MOSTLY_GENERAL=0|1: the work-list act path never / always (tests); -1: by the hint
     int rest_recent = 0;        // steps left to keep the launch on the second stream after the last non-empty list seen
     int reg_apar = 0;   // which of the two lists of newly ambiguous indices this step's registry blocks fill (trace_lane_kernel's launch) and its scan blocks read (apply_kernel's)
-    int n_groups = 1;
-    int env_lanes = 0;     // books per env_kernel wave: 0 = by batch size, or 16 / 32 / 64; 256 = env_compact_kernel (LOB_ENV_LANES, read by lob_create)
-    int reset_lanes = 64;  // books per reset_kernel wave (LOB_RESET_LANES)
     int td_parity = 0;
     int step_id = 0;            // stamps the memo claims of one step
     int list_par = 0;           // parity of the fast path's work lists
     int last_par = 0;           // `par` of the most recent step (its memo list is the current one)
     int n_cus = 256;            // compute units: the persistent learner kernels run one block on each
-    int track_ring = 4096;      // longest resident market track, in events per book; longer streams keep a ring of this many (LOB_TRACK_RING)
-    int track_refill = 64;      // steps between refills of the ring (LOB_TRACK_REFILL)
     bool chunked = false;       // the loaded stream is longer than the ring
     int steps_since_fill = 0;
     uint64_t theta_ver = 1;     // bumped whenever theta changes: memo records carry the version they were computed under
     bool half_open = false;     // between lob_td_step_begin and lob_td_step_end
     bool hits_ok = false;       // the previous call was a fast-path learner step and nothing has touched weights, maps or states since:
                                 // the hit lists its learn kernel left are those of the States the next step acts on (act_light_kernel)
-    bool light = true;          // use them (LOB_NO_LIGHT=1: always the full act kernel, for A/B runs)
-    bool force_fuse_act = false;
-    bool fuse_act = true;       // ... inside the env kernel (env_kernel<.., 1>; LOB_NO_FUSE_ACT=1: act_light_kernel as a launch of its own)
- bool t_light = true;        // trace_light_kernel in front of the wave-per-book trace kernel (Q(lambda); LOB_NO_TLIGHT=1: off)
-    bool inline_general = true; // ... serving the books without a hit list itself (LOB_INLINE_GENERAL=0: through the work list, two more launches)
     int steps_on_lists = 0;     // fused steps since the hit lists were last void
-    bool env_step = true;       // env_step_kernel for the fused action selection + step (LOB_ENV_STEP=0: env_kernel<64, 2, 1>; A/B switch)
-    bool no_fuse = false;       // LOB_NO_FUSE=1: the light trace step as a kernel of its own, not inside the lane learner kernel (A/B switch)
-    bool q_pair = true;         // ... two lanes per book (learn_q_pair_kernel; LOB_Q_PAIR=0: one)
-    int q_lanes = -1;           // learn_q_lane_kernel (a lane per book) instead of learn_q_fast_kernel (a wave per book): -1 by batch size,
-                                // 0 / 1 forced (LOB_Q_LANES)
     std::vector<void*> allocs;
     // sparse weight exchange (lob_delta_sparse_*): the ranks' gathered maps, their union, per-block counts / offsets, the packed deltas
     uint32_t* spx_gather = nullptr;
@@ -188,7 +204,6 @@ struct lob_engine {
     bool episode_open = false;  // a pre-pass ran and its window sums have not been rolled back to the stop point yet
     bool model_log = false;     // lob_model_log_enable: the step sums |delta| (td_stats_kernel)
     bool timing = false;
-    int acc_shift = -1;     // accumulate_kernel lanes per book (log2); -1: chosen from the algorithm and epsilon
     int timing_period = 1;  // kernels of every n-th step are timed (two event records per launch are not free: 9 % at n = 1)
     std::map<std::string, KTimer> timers;
     std::vector<hipEvent_t> event_pool;
@@ -238,8 +253,10 @@ template <class T> int dev_alloc(lob_engine* e, T** p, size_t count) {
 template <class T> int dev_alloc(lob_engine* e, GP<T>* p, size_t count) { return dev_alloc(e, &p->p, count); }
 
 // The device copy of DevState follows the host's (rare: a stream loaded, the exchange's buffers allocated, model_log switched on).
+// (Copied byte for byte, so that memcmp compares exactly the bytes that were uploaded, padding included.)
 int sync_state(lob_engine* e) {
-    DevState now = e->S;
+    DevState now;
+    memcpy(&now, &e->S, sizeof(DevState));
     now.cb_par = 0;
     now.cb_dense_on = 0;
     now.self = e->S_dev;
@@ -248,7 +265,7 @@ int sync_state(lob_engine* e) {
         lob_set_error("state upload failed");
         return LOB_EHIP;
     }
-    e->S_pushed = now;
+    memcpy(&e->S_pushed, &now, sizeof(DevState));
     return LOB_OK;
 }
 int push_params(lob_engine* e) {
@@ -317,6 +334,86 @@ int check_device_errors(lob_engine* e) {
     return LOB_OK;
 }
 
+// The shapes of the switches' values: set at all, to anything; "=0" / "=1" (the first character); a number in [lo, hi]; one of
+// {...}; a power of two in [lo, hi].  Anything else leaves the default.
+bool env_set(const char* n) { return getenv(n) != nullptr; }
+bool env_is(const char* n, char c) { const char* g = getenv(n); return g && g[0] == c; }
+long long env_in(const char* n, long long lo, long long hi, long long dflt) { const char* g = getenv(n); const long long v = g ? atoll(g) : dflt; return v >= lo && v <= hi ? v : dflt; }
+int env_one_of(const char* n, std::initializer_list<int> allowed, int dflt) {
+    const char* g = getenv(n);
+    for (int a : allowed) if (g && atoi(g) == a) return a;
+    return dflt;
+}
+int env_pow2(const char* n, int lo, int hi, int dflt) { const int v = (int)env_in(n, lo, hi, dflt); return (v & (v - 1)) == 0 ? v : dflt; }
+
+Switches read_switches() {
+    Switches s;
+    s.no_memo = env_is("LOB_NO_MEMO", '1'); s.no_carry = env_is("LOB_NO_CARRY", '1'); s.no_combine = env_is("LOB_NO_COMBINE", '1');
+    s.light = !env_is("LOB_NO_LIGHT", '1'); s.force_fuse_act = env_is("LOB_FUSE_ACT", '1');
+    s.t_light = !env_is("LOB_NO_TLIGHT", '1'); s.no_fuse = env_is("LOB_NO_FUSE", '1');
+    s.q_pair = !env_is("LOB_Q_PAIR", '0'); s.dq_pair = !env_is("LOB_DQ_PAIR", '0'); s.trace_lanes_off = env_is("LOB_TRACE_LANES", '0');
+    s.acc_fuse = !env_is("LOB_ACC_FUSE", '0'); s.rest_merge = !env_is("LOB_REST_MERGE", '0'); s.acc_dense = !env_is("LOB_ACC_DENSE", '0');
+    s.q_lanes = env_set("LOB_Q_LANES") ? (env_is("LOB_Q_LANES", '1') ? 1 : 0) : -1;
+    s.force_general = env_is("LOB_MOSTLY_GENERAL", '1') ? 1 : env_is("LOB_MOSTLY_GENERAL", '0') ? 0 : -1;
+    const bool exps = lobk_experiments() != 0;
+    s.env_lanes = exps ? env_one_of("LOB_ENV_LANES", {16, 32, 64, 256}, 0) : env_one_of("LOB_ENV_LANES", {16, 64}, 0);
+    s.env16_max = (int)env_in("LOB_ENV16_MAX", 0, INT_MAX, s.env16_max);
+    s.acc_batches = env_one_of("LOB_ACC_BATCHES", {1, 2, 4, 8}, 0);
+    const int acc_lanes = env_one_of("LOB_ACC_LANES", {8, 16, 32, 64}, 0);
+    s.acc_shift = acc_lanes ? __builtin_ctz(acc_lanes) : -1;
+    s.cb_slots = env_pow2("LOB_CB_SLOTS", 64, 1 << 24, 0); s.ow_slots = env_pow2("LOB_OW_SLOTS", 64, 1 << 26, 0);
+    s.amb_cap = (int)env_in("LOB_AMB_CAP", 1, 1 << 18, 0); s.cbd_ids = (int)env_in("LOB_CBD_IDS", 8, LOB_CBD_CAP, 0);
+    s.track_ring = env_pow2("LOB_TRACK_RING", 256, 1 << 20, s.track_ring); s.track_refill = (int)env_in("LOB_TRACK_REFILL", 1, INT_MAX, s.track_refill);
+    s.upload_piece_recs = env_in("LOB_UPLOAD_PIECE_RECS", 1, LLONG_MAX, 0); s.upload_pinned = !env_is("LOB_UPLOAD_PINNED", '0');
+    s.spx_count = env_in("LOB_SPX_COUNT", 64, LLONG_MAX, 0);
+    if (!exps) return s;
+    s.fuse_act = !env_is("LOB_NO_FUSE_ACT", '1'); s.inline_general = !env_is("LOB_INLINE_GENERAL", '0'); s.env_step = !env_is("LOB_ENV_STEP", '0');
+    s.prepass_roles = env_is("LOB_PREPASS_ROLES", '1'); s.sarsa_lanes_off = env_is("LOB_SARSA_LANES", '0'); s.dq_fast_off = env_is("LOB_DQ_FAST", '0');
+    s.rest_side = !env_is("LOB_REST_SIDE", '0'); s.acc_block = !env_is("LOB_ACC_BLOCK", '0');
+    s.exp_learn_first = env_set("LOB_SARSA_LEARN_FIRST"); s.no_hint = env_set("LOB_NO_HINT");
+    s.env_step_lanes = env_one_of("LOB_ENV_STEP_LANES", {32}, s.env_step_lanes); s.reset_lanes = env_one_of("LOB_RESET_LANES", {16, 32, 64}, s.reset_lanes);
+    s.n_groups = (int)env_in("LOB_GROUPS", 1, 2, s.n_groups); s.acc_reps = env_pow2("LOB_ACC_REPS", 1, 64, 0);
+    s.ts_lds = (int)env_in("LOB_TS_LDS", INT_MIN, INT_MAX, 0); s.ts_grid = (int)env_in("LOB_TS_GRID", INT_MIN, INT_MAX, 0);
+    return s;
+}
+
+// The kernel paths fixed for the engine's life.  `P`: the engine's reading of lob_params (algorithm, theta mode, record shape, trace ring).
+EnginePlan plan_paths(const DevParams& P, int B, int n_cus, const Switches& sw) {
+    EnginePlan pl;
+    const bool sarsa = P.algo == LOB_ALGO_SARSA, ql = P.algo == LOB_ALGO_QLAMBDA, dq = P.algo == LOB_ALGO_DOUBLE_Q;
+    pl.groups = B >= 1024 ? sw.n_groups : 1;   // (small batches: one group -- an empty group would be an empty launch)
+    pl.combine = !P.theta_private && !sw.no_combine;
+    pl.env_lanes = sw.env_lanes ? sw.env_lanes : (B <= 16384 ? 16 : 64);  // (16: the batch is too small to give every SIMD a wave of 64)
+    // (batches of 1 024 books and more, env_kernel<64>: the action selection rides in the env kernel -- 4 096 books: 25.0 -> 27.2 M
+    // env-steps/s, 16 384: 65.5 -> 75.8 M); up to env16_max books, a book's levels across 16 lanes (layout: lob_envstep.h)
+    pl.fused_act_ok = sw.light && sw.fuse_act && sw.env_lanes == 0 && (B >= 1024 || sw.force_fuse_act);
+    pl.env_step = P.T <= 2 && sw.env_step;
+    pl.half_waves = sw.env_step_lanes == 32 && pl.env_step && !dq;
+    pl.inline_ok = pl.env_step && sw.inline_general && !pl.half_waves;
+    pl.env16 = !dq && B <= sw.env16_max && P.D <= 16 && P.Wd <= 64;
+    // Q(s', .) + TD error: a lane per book once the batch gives every CU a full block of them, else a wave per book; the lane
+    // kernel then also takes the light trace step of the books it can (those left go on a list for the trace kernel behind it)
+    pl.q_lanes = sw.q_lanes >= 0 ? sw.q_lanes == 1 : (long long)B >= (long long)LOB_QL_BLOCK * n_cus / 2;
+    pl.q_pair = sw.q_pair && P.M < (1ll << 27) && (!dq || sw.dq_pair);  // (its LDS rows hold tile indices in 27 bits)
+    pl.t_light = (ql || dq) && sw.t_light;
+    pl.fuse = pl.t_light && pl.q_lanes && !sw.no_fuse;
+    // group-0 memo: shared theta, one book group.  Double Q only through the kernels that know two weight vectors: the fused
+    // env_step_kernel, the lane learn kernel with the fused Watkins trace step, the lane trace kernel behind it
+    pl.memo = !P.theta_private && !P.r_learn && sw.n_groups == 1 && !sw.no_memo;
+    if (dq) pl.memo = pl.memo && pl.fuse && pl.fused_act_ok && pl.env_step && pl.combine && P.trace_gens == 32 && !sw.dq_fast_off;
+    pl.carry_verdicts = !P.theta_private && !sw.no_carry && !pl.memo;  // (the memo path never reads the carry-over filter)
+    // the trace step with a lane per generation + the tile registry it needs: every book of SARSA(lambda); the books of Q(lambda)
+    // / double Q whose traces survive, listed by the lane learn kernel
+    pl.sarsa_lanes = pl.memo && pl.combine && P.trace_gens == 32 && !sw.sarsa_lanes_off && !sw.trace_lanes_off && (sarsa || pl.fuse);
+    pl.acc_block_ok = sw.acc_block && pl.memo && B >= 4 * LOB_ACB_BLOCK;
+    // (SARSA(lambda) sums per block always, Q(lambda) once most actions are greedy)
+    pl.dense_ids = pl.acc_block_ok && pl.combine && sw.acc_dense && (sarsa || ql) && P.trace_gens <= LOB_TRACE_GENS;
+    pl.acc_fuse_ok = pl.fuse && sw.acc_fuse && pl.combine && pl.sarsa_lanes && (ql || dq) && pl.groups == 1;
+    pl.rest_side_ok = pl.fuse && sw.rest_side;
+    pl.learn_first = sw.exp_learn_first && sarsa;
+    return pl;
+}
+
 }  // namespace
 
 extern "C" {
@@ -368,6 +465,11 @@ int lob_create(const lob_params* p, int32_t n_books, int32_t device, lob_engine*
     e->device = device;
     e->B = n_books;
     e->params = *p;
+    e->sw = read_switches();
+    {   // (the persistent learner kernels run one block on each CU)
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) e->n_cus = prop.multiProcessorCount;
+    }
     // from here on every failure path releases what exists so far (lob_destroy copes with null members)
 #define HIPCHK_E(expr)                                                                       \
     do {                                                                                     \
@@ -385,29 +487,6 @@ int lob_create(const lob_params* p, int32_t n_books, int32_t device, lob_engine*
     HIPCHK_E(hipEventCreateWithFlags(&e->ev_stagger, hipEventDisableTiming | hipEventDisableSystemFence));
     HIPCHK_E(hipEventCreateWithFlags(&e->ev_rest_go, hipEventDisableTiming | hipEventDisableSystemFence));
     HIPCHK_E(hipEventCreateWithFlags(&e->ev_rest_done, hipEventDisableTiming | hipEventDisableSystemFence));
-    // Runtime switches.  Honoured by every build: the A/B switches of first-class paths that the parity tests force on or off at
-    // sizes that would not select them (LOB_TRACE_LANES, LOB_Q_LANES, LOB_Q_PAIR, LOB_DQ_PAIR, LOB_NO_TLIGHT, LOB_NO_MEMO, LOB_NO_LIGHT,
-    // LOB_NO_FUSE, LOB_NO_COMBINE, LOB_NO_CARRY, LOB_MOSTLY_GENERAL, LOB_FUSE_ACT, LOB_ENV_LANES=16|64, LOB_ACC_LANES, LOB_ACC_FUSE,
-    // LOB_ACC_DENSE, LOB_ACC_BATCHES, LOB_REST_MERGE), the table sizes the tests squeeze (LOB_CB_SLOTS, LOB_OW_SLOTS, LOB_AMB_CAP, LOB_CBD_IDS), the track
-    // ring (LOB_TRACK_RING, LOB_TRACK_REFILL) and the exchange's form (LOB_DENSE_EXCHANGE, lob_comm.cpp).  The switches of variants
-    // measured and lost, and of timing experiments, only by a -DLOB_EXPERIMENTS build (tools/exp_variants.sh; NOTES.md): `exps`.
-    const bool exps = lobk_experiments() != 0;
-    if (const char* g = getenv("LOB_REST_SIDE")) e->rest_side = !(exps && g[0] == '0');
-    if (const char* g = getenv("LOB_ACC_BLOCK")) e->acc_block = !(exps && g[0] == '0');
-    if (const char* g = getenv("LOB_DQ_PAIR")) e->dq_pair = !(g[0] == '0');
-    if (const char* g = getenv("LOB_REST_MERGE")) e->rest_merge = !(g[0] == '0');
-    if (exps) {
-        if (const char* g = getenv("LOB_TS_LDS")) e->ts_lds = atoi(g);
-        e->exp_learn_first = getenv("LOB_SARSA_LEARN_FIRST") != nullptr;
-        if (const char* g = getenv("LOB_TS_GRID")) e->ts_grid = atoi(g);
-        e->no_hint = getenv("LOB_NO_HINT") != nullptr;
-    }
-    if (const char* g = getenv("LOB_ACC_DENSE")) e->acc_dense = !(g[0] == '0');
-    if (const char* g = getenv("LOB_ACC_FUSE")) e->acc_fuse = !(g[0] == '0');
-    if (const char* g = getenv("LOB_ACC_BATCHES")) { const int v = atoi(g); if (v == 1 || v == 2 || v == 4 || v == 8) { e->acc_batches = v; e->acc_batches_set = true; } }
-    if (const char* g = getenv("LOB_ENV_STEP_LANES")) { if (exps && atoi(g) == 32) e->env_step_lanes = 32; }
-    if (const char* g = getenv("LOB_ENV16_MAX")) { const int v = atoi(g); if (v >= 0) e->env16_max = v; }
-    if (const char* g = getenv("LOB_PREPASS_ROLES")) e->prepass_roles = exps && g[0] == '1';
     if (hipHostMalloc((void**)&e->rest_hint, LOB_HINT_RING * sizeof(u64), hipHostMallocMapped) == hipSuccess) {
         memset(e->rest_hint, 0, LOB_HINT_RING * sizeof(u64));
         if (hipHostGetDevicePointer((void**)&e->rest_hint_dev, e->rest_hint, 0) != hipSuccess) e->rest_hint_dev = nullptr;
@@ -415,27 +494,6 @@ int lob_create(const lob_params* p, int32_t n_books, int32_t device, lob_engine*
     if (!e->rest_hint_dev && e->rest_hint) { hipHostFree(e->rest_hint); e->rest_hint = nullptr; }
     // (these events DO fence to system scope: the host reads the word the kernel in front of them stored to host memory)
     for (int i = 0; i < LOB_HINT_RING && e->rest_hint; i++) HIPCHK_E(hipEventCreateWithFlags(&e->hint_ev[i], hipEventDisableTiming));
-    if (const char* g = getenv("LOB_MOSTLY_GENERAL")) e->force_general = g[0] == '1' ? 1 : g[0] == '0' ? 0 : -1;
-    // Optional (LOB_GROUPS=2): two book groups pipelined on two streams so that the latency-bound env
-    // kernel of one group runs beside a gather kernel of the other.  It paid 7 % before the market
-    // track made the env kernel cheap; now one group is as fast and gives clean per-kernel timings.
-    e->n_groups = 1;
-    if (const char* g = getenv("LOB_GROUPS")) { int v = atoi(g); if (exps && v >= 1 && v <= 2) e->n_groups = v; }
-    // experiment / test switches for the books-per-wave choice of the lane-per-book kernels (32 and 256 = env_compact_kernel: experiments)
-    if (const char* g = getenv("LOB_ENV_LANES")) { int v = atoi(g); if (v == 16 || v == 64 || (exps && (v == 32 || v == 256))) e->env_lanes = v; }
-    if (const char* g = getenv("LOB_TRACK_RING")) { int v = atoi(g); if (v >= 256 && v <= (1 << 20) && (v & (v - 1)) == 0) e->track_ring = v; }
-    if (const char* g = getenv("LOB_TRACK_REFILL")) { int v = atoi(g); if (v >= 1) e->track_refill = v; }
-    if (const char* g = getenv("LOB_ACC_LANES")) { int v = atoi(g); if (v == 8 || v == 16 || v == 32 || v == 64) e->acc_shift = v == 8 ? 3 : v == 16 ? 4 : v == 32 ? 5 : 6; }
-    if (const char* g = getenv("LOB_NO_LIGHT")) e->light = !(g[0] == '1');
-    if (const char* g = getenv("LOB_NO_FUSE_ACT")) e->fuse_act = !(exps && g[0] == '1');
-    if (const char* g = getenv("LOB_FUSE_ACT")) e->force_fuse_act = g[0] == '1';  // (also for small batches: the tests)
-    if (const char* g = getenv("LOB_Q_LANES")) e->q_lanes = g[0] == '1' ? 1 : 0;
-    if (const char* g = getenv("LOB_NO_TLIGHT")) e->t_light = !(g[0] == '1');
-    if (const char* g = getenv("LOB_Q_PAIR")) e->q_pair = !(g[0] == '0');
-    if (const char* g = getenv("LOB_NO_FUSE")) e->no_fuse = g[0] == '1';
-    if (const char* g = getenv("LOB_ENV_STEP")) e->env_step = !(exps && g[0] == '0');
-    if (const char* g = getenv("LOB_INLINE_GENERAL")) e->inline_general = !(exps && g[0] == '0');
-    if (const char* g = getenv("LOB_RESET_LANES")) { int v = atoi(g); if (v == 64 || (exps && (v == 16 || v == 32))) e->reset_lanes = v; }
 
     // ---- DevParams ----
     DevParams& P = e->P;
@@ -465,44 +523,14 @@ int lob_create(const lob_params* p, int32_t n_books, int32_t device, lob_engine*
     P.algo = p->algo == LOB_ALGO_R_LEARN ? LOB_ALGO_QLAMBDA : p->algo == LOB_ALGO_ONLINE_R_LEARN ? LOB_ALGO_SARSA
              : p->algo == LOB_ALGO_DOUBLE_R_LEARN ? LOB_ALGO_DOUBLE_Q : p->algo;
     P.theta_private = p->theta_mode == LOB_THETA_PRIVATE;
-    { const char* nc = getenv("LOB_NO_CARRY"); P.carry_verdicts = !P.theta_private && !(nc && nc[0] == '1'); }
-    { const char* nc = getenv("LOB_NO_COMBINE"); P.combine = !P.theta_private && !(nc && nc[0] == '1'); }
-    {   // group-0 memo: shared theta, one weight vector, one book group
-        const char* nc = getenv("LOB_NO_MEMO");
-        P.memo = !P.theta_private && !P.r_learn && e->n_groups == 1 && !(nc && nc[0] == '1');
-        const bool dq = P.algo == LOB_ALGO_DOUBLE_Q;
-        if (dq && P.memo) {
-            // DoubleQLearn on the fast path: through the kernels that know two weight vectors -- env_step_kernel<., true> (two trade
-            // slots), learn_q_lane_kernel<LOB_ALGO_DOUBLE_Q> with the fused Watkins trace step (a lane per book: big batches, or
-            // LOB_Q_LANES=1), the lane trace kernel behind it.  Anything else: the general kernels, as before.
-            hipDeviceProp_t prop;
-            int n_cus = e->n_cus;
-            if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) n_cus = prop.multiProcessorCount;
-            const bool q_lanes = e->q_lanes >= 0 ? e->q_lanes == 1 : (long long)n_books >= (long long)LOB_QL_BLOCK * n_cus / 2;
-            const char* dqf = exps ? getenv("LOB_DQ_FAST") : nullptr;
-            P.memo = q_lanes && e->t_light && !e->no_fuse && e->light && e->fuse_act && e->env_step && e->env_lanes == 0 && P.T <= 2 && P.combine &&
-                     P.trace_gens == 32 && (n_books >= 1024 || e->force_fuse_act) && !(dqf && dqf[0] == '0');
-        }
-        // the memo path never reads the carry-over filter, and its hot counter serialises first writes
-        if (P.memo) P.carry_verdicts = 0;
-        // SARSA(lambda): the trace step with a lane per generation (trace_sarsa_kernel, lob_fast.h) + the tile registry it needs
-        // ... for every book of SARSA(lambda); for Q(lambda) where the lane-per-book learn kernel takes the light trace steps and
-        // lists the books that keep their traces (the same condition as in run_steps: big batches; LOB_TRACE_LANES=0 switches it off)
-        const char* sl = exps ? getenv("LOB_SARSA_LANES") : nullptr;
-        const char* tl = getenv("LOB_TRACE_LANES");
-        bool lanes_ok = P.memo && P.combine && P.trace_gens == 32 && !(sl && sl[0] == '0') && !(tl && tl[0] == '0');
-        if (lanes_ok && (P.algo == LOB_ALGO_QLAMBDA || dq)) {
-            hipDeviceProp_t prop;
-            int n_cus = e->n_cus;
-            if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) n_cus = prop.multiProcessorCount;
-            const bool q_lanes = e->q_lanes >= 0 ? e->q_lanes == 1 : (long long)n_books >= (long long)LOB_QL_BLOCK * n_cus / 2;
-            lanes_ok = e->t_light && q_lanes && !e->no_fuse;
-        } else if (P.algo != LOB_ALGO_SARSA) lanes_ok = false;
-        P.sarsa_lanes = lanes_ok;
-        P.epi_epoch = 0;
-    }
+    e->plan = plan_paths(P, n_books, e->n_cus, e->sw);
+    P.combine = e->plan.combine;
+    P.memo = e->plan.memo;
+    P.carry_verdicts = e->plan.carry_verdicts;
+    P.sarsa_lanes = e->plan.sarsa_lanes;
+    P.epi_epoch = 0;
     P.seed = p->seed; P.book_id_offset = p->book_id_offset;
-    P.exp_learn_first = e->exp_learn_first ? 1 : 0;
+    P.exp_learn_first = e->sw.exp_learn_first ? 1 : 0;
 
     // ---- DevState ----
     DevState& S = e->S;
@@ -510,25 +538,18 @@ int lob_create(const lob_params* p, int32_t n_books, int32_t device, lob_engine*
     const size_t B = (size_t)n_books;
     S.B = n_books; S.D = P.D; S.T = P.T; S.W = P.W;
     int rc = LOB_OK;
-#define X(t, n) if (rc == LOB_OK) rc = dev_alloc(e, &S.n, B);
+    auto alloc = [&](auto* ptr, size_t count) { if (rc == LOB_OK) rc = dev_alloc(e, ptr, count); };   // (the first failure sticks)
+#define X(t, n) alloc(&S.n, B);
     LOB_ENV_FIELDS(X)
 #undef X
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.hdr, B);
+    alloc(&S.hdr, B);
     auto alloc_rm = [&](RMPtrs& r, int w) {
         r.w = w;
-        if (rc == LOB_OK) rc = dev_alloc(e, &r.ring, B * w);
-        if (rc == LOB_OK) rc = dev_alloc(e, &r.cnt, B);
-        if (rc == LOB_OK) rc = dev_alloc(e, &r.head, B);
-        if (rc == LOB_OK) rc = dev_alloc(e, &r.sum, B);
-        if (rc == LOB_OK) rc = dev_alloc(e, &r.mean, B);
-        if (rc == LOB_OK) rc = dev_alloc(e, &r.s, B);
+        alloc(&r.ring, B * w); alloc(&r.cnt, B); alloc(&r.head, B); alloc(&r.sum, B); alloc(&r.mean, B); alloc(&r.s, B);
     };
     auto alloc_acc = [&](AccPtrs& r, int w) {
         r.w = w;
-        if (rc == LOB_OK) rc = dev_alloc(e, &r.ring, B * w);
-        if (rc == LOB_OK) rc = dev_alloc(e, &r.cnt, B);
-        if (rc == LOB_OK) rc = dev_alloc(e, &r.head, B);
-        if (rc == LOB_OK) rc = dev_alloc(e, &r.sum, B);
+        alloc(&r.ring, B * w); alloc(&r.cnt, B); alloc(&r.head, B); alloc(&r.sum, B);
     };
     alloc_rm(S.f_midprice, p->lb_mpm);
     alloc_rm(S.f_volatility, p->lb_vlt);
@@ -540,68 +561,42 @@ int lob_create(const lob_params* p, int32_t n_books, int32_t device, lob_engine*
     alloc_rm(S.tp_mp, p->lb_target);
     alloc_acc(S.f_vwap_numer, p->lb_vwap);
     alloc_acc(S.f_vwap_denom, p->lb_vwap);
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.meta, B);
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.prep, B);
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.ewma_up, B);
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.ewma_down, B);
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.tp_val, B);
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.persist, B * LOB_PERSIST_N);
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.k_stop, B);
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.vars, B * 3 * 16);
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.qs_last, B * LOB_N_ACTIONS);
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.tr_idx, B * (size_t)P.trace_gens * 32);
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.tr_alive, B * (size_t)P.trace_gens);
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.theta, (size_t)P.M * (P.theta_private ? B : 1));
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.theta_nz, LOB_NZ_NWORDS(P.M) * (P.theta_private ? B : 1));
+    alloc(&S.meta, B); alloc(&S.prep, B); alloc(&S.ewma_up, B); alloc(&S.ewma_down, B); alloc(&S.tp_val, B); alloc(&S.persist, B * LOB_PERSIST_N);
+    alloc(&S.k_stop, B); alloc(&S.vars, B * 3 * 16); alloc(&S.qs_last, B * LOB_N_ACTIONS); alloc(&S.tr_idx, B * (size_t)P.trace_gens * 32);
+    alloc(&S.tr_alive, B * (size_t)P.trace_gens); alloc(&S.theta, (size_t)P.M * (P.theta_private ? B : 1));
+    alloc(&S.theta_nz, LOB_NZ_NWORDS(P.M) * (P.theta_private ? B : 1));
     if (P.algo == LOB_ALGO_DOUBLE_Q) {
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.theta_b, (size_t)P.M * (P.theta_private ? B : 1));
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.theta_b_nz, LOB_NZ_NWORDS(P.M) * (P.theta_private ? B : 1));
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.qs_last_b, B * LOB_N_ACTIONS);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.mt_state, B * LOB_MT_N);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.mt_idx, B);
+        alloc(&S.theta_b, (size_t)P.M * (P.theta_private ? B : 1)); alloc(&S.theta_b_nz, LOB_NZ_NWORDS(P.M) * (P.theta_private ? B : 1));
+        alloc(&S.qs_last_b, B * LOB_N_ACTIONS); alloc(&S.mt_state, B * LOB_MT_N); alloc(&S.mt_idx, B);
     }
     {
         const bool rl = P.r_learn != 0;
         const size_t nr = rl ? (P.theta_private ? B : 1) : 1;
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.rho, nr);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.rho_inc, nr);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.rho_cnt, nr);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.rl_t, rl ? B : 1);
+        alloc(&S.rho, nr); alloc(&S.rho_inc, nr); alloc(&S.rho_cnt, nr); alloc(&S.rl_t, rl ? B : 1);
     }
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.tr_sig, B * (size_t)P.trace_gens * 4);
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.tr_cbslot, B * (size_t)P.trace_gens);
+    alloc(&S.tr_sig, B * (size_t)P.trace_gens * 4); alloc(&S.tr_cbslot, B * (size_t)P.trace_gens);
     {
         // (slots persist while in use: room for the generations of a few steps; LOB_CB_SLOTS overrides, for the tests)
         int slots = 2048;
         while ((size_t)slots < 8 * B && slots < (1 << 22)) slots <<= 1;
-        if (const char* g = getenv("LOB_CB_SLOTS")) { int v = atoi(g); if (v >= 64 && v <= (1 << 24) && (v & (v - 1)) == 0) slots = v; }
+        if (e->sw.cb_slots) slots = e->sw.cb_slots;
         S.cb_slots = slots;
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.cb_key, (size_t)slots);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.cb_ident, (size_t)slots * 8);
+        alloc(&S.cb_key, (size_t)slots); alloc(&S.cb_ident, (size_t)slots * 8);
         // SARSA(lambda) adds 1.6 M terms per step to the slots' sums: a copy of the sums per XCD (0.147 -> 0.100 ms; apply_kernel
         // 0.023 -> 0.03); Q(lambda)'s few additions are a latency chain that the copies do not shorten
         // ... and so do Watkins's Q(lambda) / double Q once the policy is mostly greedy (epsilon decays over the episodes: no cut,
         // 25 generations per book, and the greedy books crowd onto a few (triple, action) pairs: 0.44 ms per step with one copy at
         // epsilon = 0.01).  One copy per XCD for every algorithm on the fast path; apply_kernel adds them up.
-        S.cb_reps = P.memo ? 8 : 1;
-        if (const char* g = getenv("LOB_ACC_REPS")) { int v = atoi(g); if (exps && (v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64)) S.cb_reps = v; }
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.cb_acc, (size_t)S.cb_reps * slots * 2);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.cb_touch, (size_t)slots);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.cb_list, 2 * (size_t)slots);
+        S.cb_reps = e->sw.acc_reps ? e->sw.acc_reps : P.memo ? 8 : 1;
+        alloc(&S.cb_acc, (size_t)S.cb_reps * slots * 2); alloc(&S.cb_touch, (size_t)slots); alloc(&S.cb_list, 2 * (size_t)slots);
         S.cb_segs = std::min(2048, slots / 4);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.cb_count, 2 * (size_t)S.cb_segs);
+        alloc(&S.cb_count, 2 * (size_t)S.cb_segs);
         if (rc == LOB_OK && hipMemsetAsync(S.cb_key, 0xff, (size_t)slots * 8, e->stream) != hipSuccess) rc = LOB_EHIP;
-        // dense ids of the slots (lob_state.h; accumulate_dense_kernel): for the algorithms whose update can come to sum per block
-        // (SARSA(lambda) always, Q(lambda) once most actions are greedy), on the fast path, big batches
-        const bool dense_ok = P.memo && P.combine && e->acc_dense && e->acc_block && (P.algo == LOB_ALGO_SARSA || P.algo == LOB_ALGO_QLAMBDA) &&
-                              (long long)n_books >= 4 * LOB_ACB_BLOCK && P.trace_gens <= LOB_TRACE_GENS;
-        if (dense_ok) {
-            if (rc == LOB_OK) rc = dev_alloc(e, &S.cb_dense, (size_t)slots);
-            if (rc == LOB_OK) rc = dev_alloc(e, &S.cb_free, (size_t)LOB_CBD_CAP);
-            if (rc == LOB_OK) rc = dev_alloc(e, &S.cb_free_n, 16);
-            if (rc == LOB_OK) rc = dev_alloc(e, &S.tr_cbd, B * (size_t)P.trace_gens);
-            if (rc == LOB_OK) rc = dev_alloc(e, &S.cb_part, (size_t)LOB_ACD_MAX_BLOCKS * LOB_CBD_CAP);
-            if (rc == LOB_OK) rc = dev_alloc(e, &S.cb_red, (size_t)LOB_ACD_GROUPS * LOB_CBD_CAP);
+        // dense ids of the slots (EnginePlan::dense_ids)
+        if (e->plan.dense_ids) {
+            alloc(&S.cb_dense, (size_t)slots); alloc(&S.cb_free, (size_t)LOB_CBD_CAP); alloc(&S.cb_free_n, 16);
+            alloc(&S.tr_cbd, B * (size_t)P.trace_gens); alloc(&S.cb_part, (size_t)LOB_ACD_MAX_BLOCKS * LOB_CBD_CAP);
+            alloc(&S.cb_red, (size_t)LOB_ACD_GROUPS * LOB_CBD_CAP);
             if (rc == LOB_OK && hipMemsetAsync(S.cb_dense, 0xff, (size_t)slots * 4, e->stream) != hipSuccess) rc = LOB_EHIP;
             if (rc == LOB_OK && hipMemsetAsync(S.tr_cbd, 0xff, B * (size_t)P.trace_gens * 8, e->stream) != hipSuccess) rc = LOB_EHIP;
             if (rc == LOB_OK) {
@@ -610,7 +605,7 @@ int lob_create(const lob_params* p, int32_t n_books, int32_t device, lob_engine*
                 std::vector<i32> fl(LOB_CBD_CAP), fn(16);
                 const int per = LOB_CBD_CAP / 8;
                 int have = per;
-                if (const char* g = getenv("LOB_CBD_IDS")) { const int v = atoi(g); if (v >= 8 && v <= LOB_CBD_CAP) have = v / 8; }
+                if (e->sw.cbd_ids) have = e->sw.cbd_ids / 8;
                 S.cb_ids = have * 8;
                 for (int x = 0; x < 8; x++) {
                     for (int i = 0; i < have; i++) fl[(size_t)x * per + i] = (have - 1 - i) * 8 + x;
@@ -630,29 +625,13 @@ int lob_create(const lob_params* p, int32_t n_books, int32_t device, lob_engine*
     {
         S.mk_slots = 1 << 16;
         const size_t ms = (size_t)S.mk_slots;
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.mk_hash, ms);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.mk_ident, ms * 4);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.mk_stamp, ms);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.mk_list, 2 * ms);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.mk_count, 2);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.mk_rec, 2 * ms * LOB_MK_REC);
-        if (P.memo && P.algo == LOB_ALGO_DOUBLE_Q && rc == LOB_OK) rc = dev_alloc(e, &S.mk_rec_b, 2 * ms * LOB_MK_REC);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.mk_tiles, P.memo ? ms * LOB_N_ACTIONS * 32 : 1);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.mk_tiles_ok, ms);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.mk_marked, ms);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.mk_marklist, ms);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.mk_markcount, 1);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.tr_list, B);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.tr_list_n, 2);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.tr_list2, B);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.tr_list2_n, 2);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.acc_list, B);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.acc_list_n, 2);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.acc_pend, B);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.dir_list, P.combine ? B * (size_t)P.trace_gens : 1);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.dir_list_n, 2);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.mk_slot, B);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.mk_slot_last, B);
+        alloc(&S.mk_hash, ms); alloc(&S.mk_ident, ms * 4); alloc(&S.mk_stamp, ms); alloc(&S.mk_list, 2 * ms); alloc(&S.mk_count, 2);
+        alloc(&S.mk_rec, 2 * ms * LOB_MK_REC);
+        if (P.memo && P.algo == LOB_ALGO_DOUBLE_Q) alloc(&S.mk_rec_b, 2 * ms * LOB_MK_REC);
+        alloc(&S.mk_tiles, P.memo ? ms * LOB_N_ACTIONS * 32 : 1); alloc(&S.mk_tiles_ok, ms); alloc(&S.mk_marked, ms); alloc(&S.mk_marklist, ms);
+        alloc(&S.mk_markcount, 1); alloc(&S.tr_list, B); alloc(&S.tr_list_n, 2); alloc(&S.tr_list2, B); alloc(&S.tr_list2_n, 2);
+        alloc(&S.acc_list, B); alloc(&S.acc_list_n, 2); alloc(&S.acc_pend, B); alloc(&S.dir_list, P.combine ? B * (size_t)P.trace_gens : 1);
+        alloc(&S.dir_list_n, 2); alloc(&S.mk_slot, B); alloc(&S.mk_slot_last, B);
         if (rc == LOB_OK && hipMemsetAsync(S.mk_hash, 0xff, ms * 8, e->stream) != hipSuccess) rc = LOB_EHIP;
         if (rc == LOB_OK && hipMemsetAsync(S.mk_slot, 0xff, B * 4, e->stream) != hipSuccess) rc = LOB_EHIP;
         if (rc == LOB_OK && hipMemsetAsync(S.mk_slot_last, 0xff, B * 4, e->stream) != hipSuccess) rc = LOB_EHIP;
@@ -662,17 +641,11 @@ int lob_create(const lob_params* p, int32_t n_books, int32_t device, lob_engine*
         S.amb_cap = sl ? (int)std::min<long long>((long long)P.M, 1 << 18) : 1;
         // (LOB_OW_SLOTS / LOB_AMB_CAP: tiny values for the tests -- a registry without room leaves slots unregistered, a full list
         // of new ambiguous indices switches the lane kernel off until the next reset: every book then goes to the wave-per-book kernel)
-        if (sl) if (const char* g = getenv("LOB_OW_SLOTS")) { int v = atoi(g); if (v >= 64 && v <= (1 << 26) && (v & (v - 1)) == 0) S.ow_slots = v; }
-        if (sl) if (const char* g = getenv("LOB_AMB_CAP")) { int v = atoi(g); if (v >= 1 && v <= (1 << 18)) S.amb_cap = v; }
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.tr_mslot, sl ? B * (size_t)P.trace_gens : 1);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.ow_tab, (size_t)S.ow_slots);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.amb_bits, sl ? (size_t)P.M / 32 + 1 : 1);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.amb_new, 2 * (size_t)S.amb_cap);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.amb_new_n, 2);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.amb_flag, 1);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.mk_amb, sl ? ms * LOB_N_ACTIONS : 1);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.mk_all, sl ? ms : 1);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.mk_all_n, 1);
+        if (sl && e->sw.ow_slots) S.ow_slots = e->sw.ow_slots;
+        if (sl && e->sw.amb_cap) S.amb_cap = e->sw.amb_cap;
+        alloc(&S.tr_mslot, sl ? B * (size_t)P.trace_gens : 1); alloc(&S.ow_tab, (size_t)S.ow_slots);
+        alloc(&S.amb_bits, sl ? (size_t)P.M / 32 + 1 : 1); alloc(&S.amb_new, 2 * (size_t)S.amb_cap); alloc(&S.amb_new_n, 2); alloc(&S.amb_flag, 1);
+        alloc(&S.mk_amb, sl ? ms * LOB_N_ACTIONS : 1); alloc(&S.mk_all, sl ? ms : 1); alloc(&S.mk_all_n, 1);
         if (rc == LOB_OK && hipMemsetAsync(S.tr_mslot, 0xff, (sl ? B * (size_t)P.trace_gens : 1) * 4, e->stream) != hipSuccess) rc = LOB_EHIP;
         if (rc == LOB_OK && hipMemsetAsync(S.ow_tab, 0xff, (size_t)S.ow_slots * 8, e->stream) != hipSuccess) rc = LOB_EHIP;
     }
@@ -683,17 +656,11 @@ int lob_create(const lob_params* p, int32_t n_books, int32_t device, lob_engine*
         P.cshift = cs;
         const size_t cwords = (((size_t)P.M >> cs) + 32) / 32;
         P.cwords4 = (int)((cwords + 3) / 4);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.theta_nzx, P.memo ? (size_t)P.M / 32 + 1 : 1);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.theta_nzc, (size_t)P.cwords4 * 4);
-        if (P.memo && rc == LOB_OK) rc = dev_alloc(e, &S.theta_nzd, 2 * ((size_t)P.M / 32 + 1));
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.slow_list, 2 * B);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.slow_n, 4);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.hl_rec, P.memo ? (size_t)LOB_HL_REC * B : 1);
-        if (rc == LOB_OK) rc = dev_alloc(e, &S.hl_dirty, 1);
+        alloc(&S.theta_nzx, P.memo ? (size_t)P.M / 32 + 1 : 1); alloc(&S.theta_nzc, (size_t)P.cwords4 * 4);
+        if (P.memo) alloc(&S.theta_nzd, 2 * ((size_t)P.M / 32 + 1));
+        alloc(&S.slow_list, 2 * B); alloc(&S.slow_n, 4); alloc(&S.hl_rec, P.memo ? (size_t)LOB_HL_REC * B : 1); alloc(&S.hl_dirty, 1);
         if (rc == LOB_OK && hipMemsetAsync(S.hl_rec, 0xff, (P.memo ? (size_t)LOB_HL_REC * B : 1) * 8, e->stream) != hipSuccess) rc = LOB_EHIP;
         if (rc == LOB_OK && hipMemsetAsync(S.hl_dirty, 0xff, 4, e->stream) != hipSuccess) rc = LOB_EHIP;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) e->n_cus = prop.multiProcessorCount;
         if (P.memo) {
             const int q_lds = (int)fast_lds_bytes(P.cwords4, LOB_FAST_NB, false), tr_lds = (int)trace_lds_bytes();
             hipError_t er = hipFuncSetAttribute((const void*)act_fast_kernel<LOB_FAST_NB>, hipFuncAttributeMaxDynamicSharedMemorySize, q_lds);
@@ -708,22 +675,16 @@ int lob_create(const lob_params* p, int32_t n_books, int32_t device, lob_engine*
             if (er != hipSuccess && rc == LOB_OK) { lob_set_error(std::string("hipFuncSetAttribute(dynamic LDS): ") + hipGetErrorString(er)); rc = LOB_EHIP; }
         }
     }
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.verdict, B * LOB_VD_STRIDE);
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.nz_new, 4 * LOB_NZ_WORDS);
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.verdict_b, P.algo == LOB_ALGO_DOUBLE_Q ? B * 64 : 1);
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.nz_epoch, 1);
+    alloc(&S.verdict, B * LOB_VD_STRIDE); alloc(&S.nz_new, 4 * LOB_NZ_WORDS); alloc(&S.verdict_b, P.algo == LOB_ALGO_DOUBLE_Q ? B * 64 : 1);
+    alloc(&S.nz_epoch, 1);
     // (striped: lob_state.h cnt_add; [8]: generations apply_kernel applied from trace_rest_kernel's list, lob_debug_deferred)
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.counters, (size_t)LOB_CNT_STRIPES * LOB_CNT_STRIDE);
-    if (rc == LOB_OK) rc = dev_alloc(e, &e->cnt_sum, 16);
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.error_flag, 1);
+    alloc(&S.counters, (size_t)LOB_CNT_STRIPES * LOB_CNT_STRIDE); alloc(&e->cnt_sum, 16); alloc(&S.error_flag, 1);
 #ifdef LOB_PROF
-    if (rc == LOB_OK) rc = dev_alloc(e, &S.prof, B * LOB_PROF_N);
+    alloc(&S.prof, B * LOB_PROF_N);
 #endif
-    if (rc == LOB_OK) rc = dev_alloc(e, &e->rnd_dev, 2048 + 64);
+    alloc(&e->rnd_dev, 2048 + 64);
     S.nzd_terms = e->rnd_dev ? e->rnd_dev + 2048 + LOB_N_ACTIONS : nullptr;  // term[1][.], term[2][.] (filled below)
-    if (rc == LOB_OK) rc = dev_alloc(e, &e->actions_dev, B);
-    if (rc == LOB_OK) rc = dev_alloc(e, &e->P_dev, 1);
-    if (rc == LOB_OK) rc = dev_alloc(e, &e->S_dev, 1);
+    alloc(&e->actions_dev, B); alloc(&e->P_dev, 1); alloc(&e->S_dev, 1);
     if (rc == LOB_OK) { S.self = e->S_dev; memset(&e->S_pushed, 0xff, sizeof(DevState)); }
     if (rc == LOB_OK) rc = push_params(e);
     if (rc != LOB_OK) { lob_destroy(e); return rc; }
@@ -883,9 +844,9 @@ static int set_records(lob_engine* e, int32_t n_events, size_t n_rows) {
     free_days(e);
     const size_t bytes = n_rows * e->P.Wd * 4 + 256;  // (tail pad: drec_levels reads whole 16-byte quads past a short level array)
     // market track: resident (one entry per event) up to track_ring events per book, a ring of that many beyond
-    e->chunked = n_events > e->track_ring;
-    e->S.track_len = e->chunked ? e->track_ring : n_events;
-    e->S.track_mask = e->chunked ? e->track_ring - 1 : 0x7fffffff;
+    e->chunked = n_events > e->sw.track_ring;
+    e->S.track_len = e->chunked ? e->sw.track_ring : n_events;
+    e->S.track_mask = e->chunked ? e->sw.track_ring - 1 : 0x7fffffff;
     const size_t track_bytes = (size_t)e->B * e->S.track_len * sizeof(Track);
     // (a stream of the size of the one before it -- a fresh day per episode -- moves into the buffers that are there: freeing and
     // allocating 31 + 18 GB cost more than the copy of a whole stream, round 6)
@@ -980,7 +941,7 @@ static int upload_records(lob_engine* e, const uint32_t* host_records, size_t n_
     const size_t rec_bytes = (size_t)e->P.W * 4;
     const size_t bytes = n_records * rec_bytes;
     size_t piece_recs = std::max<size_t>(1, ((size_t)64 << 20) / rec_bytes);
-    if (const char* g = getenv("LOB_UPLOAD_PIECE_RECS")) { const long v = atol(g); if (v >= 1) piece_recs = (size_t)v; }  // (tests: many small pieces)
+    if (e->sw.upload_piece_recs) piece_recs = (size_t)e->sw.upload_piece_recs;  // (tests: many small pieces)
     if (n_records <= 2 * piece_recs) {
         uint32_t* tmp = nullptr;
         if (hipMalloc((void**)&tmp, bytes) != hipSuccess) { lob_set_error("hipMalloc(upload buffer) failed"); return LOB_ENOMEM; }
@@ -1011,8 +972,7 @@ static int upload_records(lob_engine* e, const uint32_t* host_records, size_t n_
         if (err == hipSuccess) err = hipEventCreateWithFlags(&done[i], hipEventDisableTiming);
     }
     if (err != hipSuccess) { release(); lob_set_error("hipMalloc(upload pieces) failed"); return LOB_ENOMEM; }
-    bool use_pinned = true;
-    if (const char* g = getenv("LOB_UPLOAD_PINNED")) use_pinned = !(g[0] == '0');
+    bool use_pinned = e->sw.upload_pinned;
     for (int i = 0; i < 2 && use_pinned; i++)
         if (hipHostMalloc(&pinned[i], piece_bytes, hipHostMallocDefault) != hipSuccess) {   // (no pinned memory to be had: the pageable pieces below)
             (void)hipGetLastError();
@@ -1260,19 +1220,16 @@ int lob_gen_events_device(lob_engine* e, const lob_gen_params* g) {
     return LOB_OK;
 }
 
-// env_kernel with 64 books per wave, or 16 when the batch is too small to give every SIMD a wave
+// env_kernel with EnginePlan::env_lanes books per wave
 static void launch_env(lob_engine* e, hipStream_t st, const i32* actions, int count_updates, int b0, int nb, int par) {
-    // (LOB_ENV_LANES: 16 | 64 forced; 32, and 256 = the event loop compacted across 256-book blocks, in experiment builds)
-    const int force = e->env_lanes;
-    const int lanes = force ? force : (e->B <= 16384 ? 16 : 64);
-    lobk_env(st, lanes, e->P.T <= 2, (const DevParams*)e->P_dev, e->S, actions, count_updates, b0, nb, e->step_id, par);
+    lobk_env(st, e->plan.env_lanes, e->P.T <= 2, (const DevParams*)e->P_dev, e->S, actions, count_updates, b0, nb, e->step_id, par);
 }
 // Long streams: let the pre-pass run on every `track_refill` steps (lob_kernels.h prepass_extend_kernel)
 static void maybe_refill_track(lob_engine* e) {
-    if (!e->chunked || ++e->steps_since_fill < e->track_refill) return;
+    if (!e->chunked || ++e->steps_since_fill < e->sw.track_refill) return;
     e->steps_since_fill = 0;
     TimedLaunch t(e, "prepass_extend_kernel", nullptr, true);
-    lobk_prepass_extend(e->stream, e->P.T <= 2, e->prepass_roles, (const DevParams*)e->P_dev, e->S);
+    lobk_prepass_extend(e->stream, e->P.T <= 2, e->sw.prepass_roles, (const DevParams*)e->P_dev, e->S);
 }
 // S0 of every group-0 triple on this step's list (lob_kernels.h memo_kernel): `which` 0 = for learn_kernel
 // (theta_t), 1 = for the next act_kernel (after the update)
@@ -1280,46 +1237,6 @@ static void launch_memo(lob_engine* e, int par, int which, int reset_lpar = -1) 
     TimedLaunch t(e, "memo_kernel");
     hipLaunchKernelGGL(memo_kernel, dim3(256), dim3(256), 0, e->stream, e->P, e->S, (const uint32_t*)e->rnd_dev, par, which, (u64)e->theta_ver, reset_lpar);
 }
-// The learner step's action selection inside the env kernel (env_kernel<64, TM, 1>), the general act kernel for the books it
-// leaves on the work list, and their steps (env_kernel<64, TM, 2>).
-static void launch_env_fused(lob_engine* e, hipStream_t st, int par, int lpar, u64 ver, const i32* act_list, const i32* act_n, int gl) {
-    const DevParams* Pd = (const DevParams*)e->P_dev;
-    const bool t2 = e->P.T <= 2;
-    const int nb = e->B, sid = e->step_id;
-    const EnvFuse F1{nullptr, nullptr, lpar, sid - 1, ver}, F2{act_list, act_n, lpar, sid - 1, ver};
-    // Two trade slots per record: env_step_kernel (lob_envstep.h; LOB_ENV_STEP=0: env_kernel<64, 2, 1>).  It serves the books
-    // without a usable hit list itself (act_book in-kernel) -- except in the first step on lists after they were void, when a late
-    // map bit of the step before has voided them again and EVERY book takes the general path: that step goes through
-    // the work list to the general act kernel and env_kernel<64, 2, 2> as before (either version is correct for any step).
-    // ... and while MOST books have no usable list (a dense weight vector -- learning.random_init, a loaded checkpoint: every tile
-    // lies on a written weight and no list fits a record): one wave per book in the general act kernel is far better than a
-    // 64-lane wave going through its books one at a time.  The learn kernels hand the same books back: their list's length
-    // of LOB_HINT_LAG steps ago (lob_engine::rest_hint) tells.
-    const bool mostly_general = e->force_general >= 0 ? e->force_general == 1 : e->hint_now > e->B / 16;
-    const bool half_waves = e->env_step_lanes == 32 && t2 && e->env_step && e->P.algo != LOB_ALGO_DOUBLE_Q;  // (experiment: LOB_ENV_STEP_LANES=32)
-    const bool inline_general = t2 && e->env_step && e->inline_general && e->steps_on_lists >= 1 && !mostly_general && !half_waves;
-    e->steps_on_lists++;
-    e->flow[inline_general ? 4 : mostly_general ? 5 : 6]++;
-    const bool dq = e->P.algo == LOB_ALGO_DOUBLE_Q;  // (then t2 && env_step: lob_create)
-    {
-        TimedLaunch t(e, "env_kernel", st);
-        // (batches up to env16_max books: a book's levels across 16 lanes, four books per wave -- env_step16_kernel)
-        const bool lanes16 = !dq && nb <= e->env16_max;
-        if (t2 && e->env_step) lobk_env_step(st, inline_general, dq, half_waves, lanes16, Pd, e->S, nb, sid, par, F1, (const uint32_t*)e->rnd_dev);
-        else lobk_env_mode(st, t2, 1, Pd, e->S, nb, sid, par, F1);
-    }
-    if (inline_general) return;
-    {
-        TimedLaunch t(e, "act_rest_kernel", st);
-        if (dq) hipLaunchKernelGGL((act_kernel<LOB_ALGO_DOUBLE_Q, true>), dim3(gl), dim3(LOB_BLOCK), 0, st, LOB_PS(e), (const uint32_t*)e->rnd_dev, 0, 0, e->B, par, act_list, act_n);
-        else hipLaunchKernelGGL((act_kernel<LOB_ALGO_SARSA, true>), dim3(gl), dim3(LOB_BLOCK), 0, st, LOB_PS(e), (const uint32_t*)e->rnd_dev, 0, 0, e->B, par, act_list, act_n);
-    }
-    {
-        TimedLaunch t(e, "env_rest_kernel", st);
-        lobk_env_mode(st, t2, 2, Pd, e->S, nb, sid, par, F2);
-    }
-}
-
 int lob_reset(lob_engine* e) {
     if (!e) return LOB_EINVAL;
     if (!e->have_events) { lob_set_error("lob_reset: no event stream loaded"); return LOB_ESTATE; }
@@ -1374,7 +1291,7 @@ int lob_reset(lob_engine* e) {
     }
     {
         TimedLaunch t(e, "reset_kernel", nullptr, true);
-        lobk_reset(e->stream, e->reset_lanes, e->P.T <= 2, e->prepass_roles, (const DevParams*)e->P_dev, e->S);
+        lobk_reset(e->stream, e->sw.reset_lanes, e->P.T <= 2, e->sw.prepass_roles, (const DevParams*)e->P_dev, e->S);
     }
     HIPCHK(hipGetLastError());
     e->was_reset = true;
@@ -1490,24 +1407,383 @@ int lob_get_books(lob_engine* e, int32_t first, int32_t n, lob_book_dump* out) {
 }
 int lob_get_book(lob_engine* e, int32_t book, lob_book_dump* out) { return lob_get_books(e, book, 1, out); }
 
-// One env-step of every book.  The books are split into n_groups contiguous
-// groups, each running act -> env -> learn on its own stream; both groups only
-// READ theta, so the synchronous-batch semantic is unchanged.  The update of all
-// books runs on the main stream after both groups have joined.
-// SARSA(lambda): every book keeps all its generations -- sums per slot inside 1 024-book blocks first (accumulate_block_kernel).
-// The same for Q(lambda) once most actions are greedy (P(greedy) = 1 - eps + eps / 9 > 0.7: more than three live generations per book)
-static bool acc_blocked(const lob_engine* e) {
-    const bool many_gens = e->P.algo == LOB_ALGO_SARSA || (e->P.algo == LOB_ALGO_QLAMBDA && e->P.policy == LOB_POLICY_EPS_GREEDY && e->P.epsilon < 0.34);
-    return e->acc_block && e->P.memo && many_gens && e->B >= 4 * LOB_ACB_BLOCK;
+// One env-step of every book (run_steps).  The books are split into EnginePlan::groups contiguous groups, each running its action
+// half (act -> env) and its learn half (memo, traces, TD errors) on its own stream; both groups only READ theta, so the
+// synchronous-batch semantic is unchanged.  The update of all books runs on the main stream after both groups have joined.
+// The choices of one step, made at the top of each call (plan_step): when a step is split in two calls, the second makes them
+// again (lob_set_epsilon may come between the halves), and what the first half read for the second stays engine state (hint_now).
+struct StepPlan {
+    bool first, second;     // the call runs the action half / the learn half and the update
+    int mode;               // 0 learner, 1 backtester (lob_eval_step)
+    bool learner, fast;     // mode 0; the memo + fast kernels (P.memo: one book group)
+    int par, lpar;          // parity of the verdict carry-over lists (lob_state.h) / of the fast path's work lists
+    u64 ver;                // theta version the step's memo records are computed under
+    bool acc_blocked, dense_on;  // the update sums per block (the books keep many generations), by the slots' dense ids
+    int acc_shift;          // accumulate_kernel's lanes per book (log2)
+    bool fused_act, mostly_general, inline_general;  // the action selection inside the env kernel; the books without a usable hit
+                                                     // list through the work list to the act kernel / served in-kernel
+    bool acc_fused;         // updates added to their slots by the learn / trace kernels, accumulate_kernel over the list they leave
+    bool rest_merged;       // ... and trace_rest_kernel instead of learn_q_rest_kernel + trace_fast_kernel<., 2> + accumulate_kernel over it
+    bool rest_side;         // learn_q_rest_kernel on the second stream beside the trace kernels
+    bool registered;        // trace_lane_kernel carries the tile registry's blocks (apply_kernel then carries the scan's)
+};
+
+// One book group's share of a step: books [b0, b0 + nb) on `st`
+struct StepGroup {
+    int g, b0, nb;
+    hipStream_t st;
+    int gw, gf, gl;   // grids: a wave per book; the persistent kernels (one 16-wave block per CU); the general kernels over a work list
+};
+static StepGroup step_group(const lob_engine* e, int g, int G) {
+    const int b0 = (int)((long long)e->B * g / G), nb = (int)((long long)e->B * (g + 1) / G) - b0;
+    return {g, b0, nb, g == 0 ? e->stream : e->stream2, grid_waves(nb),
+            std::min(e->n_cus, (nb + LOB_FAST_WAVES * LOB_FAST_NB - 1) / (LOB_FAST_WAVES * LOB_FAST_NB)), 2 * e->n_cus};
 }
-// accumulate_kernel's lanes per book (log2): one lane per trace generation.  Two books per wave measured
-// best for both SARSA(lambda) (all trace_kmax generations alive) and Watkins's Q(lambda) at eps = 0.8 (1-2
-// alive; 8 lanes per book: 0.035 ms, 16: 0.030, 32: 0.029, 64: 0.036).  LOB_ACC_LANES=8|16|32|64 overrides.
-static int acc_lanes_shift(const lob_engine* e) {
-    if (e->acc_shift >= 0) return e->acc_shift;
-    if (e->P.algo == LOB_ALGO_SARSA && e->S.cb_reps > 1) return 6;  // (with a copy of the sums per XCD: 64 lanes 0.096 ms, 32 lanes 0.101)
-    if (e->P.policy == LOB_POLICY_EPS_GREEDY && e->P.epsilon < 0.34) return 6;  // (mostly greedy: Q(lambda)'s books keep their generations like SARSA's)
-    return 5;
+
+// The learn kernels' hand-back count of LOB_HINT_LAG learner steps ago (0 until that many have run since the hints were void)
+static int read_hint(lob_engine* e, const StepPlan& sp) {
+    e->hint_now = 0;
+    if (!(sp.fast && sp.learner && e->rest_hint && e->hint_step >= LOB_HINT_LAG)) return LOB_OK;
+    // (the latest reporting step that is at least LOB_HINT_LAG steps old)
+    const int hs = (int)(((e->hint_step - LOB_HINT_LAG) / LOB_HINT_EVERY * LOB_HINT_EVERY) % LOB_HINT_RING);
+    HIPCHK(hipEventSynchronize(e->hint_ev[hs]));
+    // (the kernel is done; its store to host memory is a system-scope atomic and carries the launch's tag: wait for that very word)
+    u64 w = *(volatile u64*)(e->rest_hint + hs);
+    for (int spin = 0; (uint32_t)(w >> 32) != e->hint_tags[hs] && spin < (1 << 16); spin++) w = *(volatile u64*)(e->rest_hint + hs);
+    // The count only chooses between two correct paths: a word that has still not arrived (a loaded host, a slow link)
+    // is no reason to abort training -- this step goes by "no book handed back" (ADVICE r5), and is counted
+    // (lob_debug_hint: a test that asserts which path ran must know that the hint decided it)
+    const bool arrived = (uint32_t)(w >> 32) == e->hint_tags[hs];
+    e->hint_now = arrived ? (int)(uint32_t)w : 0;
+    e->hint_reads++;
+    if (!arrived) e->hint_misses++;
+    return LOB_OK;
+}
+
+// A launch of the kernel that reports the hand-back count to the host (learn_q_rest_kernel, or trace_rest_kernel in the merged
+// flow): `launch(hint_dev, hint_tag)`.  Every LOB_HINT_EVERY-th stores it to its ring word, with an event recorded behind it.
+extern "C++" template <class Launch> static int report_hint(lob_engine* e, hipStream_t st, Launch launch) {
+    const bool on = e->rest_hint && !e->sw.no_hint;  // (LOB_NO_HINT, experiment: the store to host memory costs the kernel 3.5 us and the step nothing)
+    const int hs = (int)(e->hint_step % LOB_HINT_RING);
+    const bool reports = on && e->hint_step % LOB_HINT_EVERY == 0;
+    const uint32_t hint_tag = (uint32_t)(++e->hint_serial);
+    launch(reports ? e->rest_hint_dev + hs : (u64*)nullptr, hint_tag);
+    if (reports) { HIPCHK(hipEventRecord(e->hint_ev[hs], st)); e->hint_tags[hs] = hint_tag; }
+    if (on) e->hint_step++;
+    return LOB_OK;
+}
+
+static int plan_step(lob_engine* e, int mode, int half, StepPlan& sp) {
+    const EnginePlan& pl = e->plan;
+    sp = StepPlan{};
+    sp.first = half != 2; sp.second = half != 1;
+    sp.mode = mode; sp.learner = mode == 0;
+    sp.fast = e->P.memo != 0;
+    sp.par = sp.learner ? (sp.first ? (e->td_parity ^= 1) : e->td_parity) : 0;
+    if (sp.first) e->step_id++;
+    if (!e->hits_ok) e->steps_on_lists = 0;
+    sp.ver = (u64)e->theta_ver;
+    if (sp.first) { const int rc = read_hint(e, sp); if (rc) return rc; }
+    sp.lpar = sp.first ? (e->list_par ^= 1) : e->list_par;
+    e->last_par = sp.par;
+    // SARSA(lambda): every book keeps all its generations -- sums per slot inside 1 024-book blocks first (accumulate_block_kernel).
+    // The same for Q(lambda) once most actions are greedy (P(greedy) = 1 - eps + eps / 9 > 0.7: more than three live generations per book)
+    const bool greedy = e->P.policy == LOB_POLICY_EPS_GREEDY && e->P.epsilon < 0.34;
+    sp.acc_blocked = pl.acc_block_ok && (e->P.algo == LOB_ALGO_SARSA || (e->P.algo == LOB_ALGO_QLAMBDA && greedy));
+    sp.dense_on = e->S.cb_dense && sp.acc_blocked;
+    // accumulate_kernel's lanes per book (log2): one lane per trace generation.  Two books per wave measured best for both SARSA(lambda)
+    // (all trace_kmax generations alive) and Watkins's Q(lambda) at eps = 0.8 (1-2 alive; 8 lanes per book: 0.035 ms, 16: 0.030, 32: 0.029,
+    // 64: 0.036); 64 lanes for SARSA(lambda) with a copy of the sums per XCD (0.096 ms, 32 lanes 0.101) and while mostly greedy
+    sp.acc_shift = e->sw.acc_shift >= 0 ? e->sw.acc_shift : (e->P.algo == LOB_ALGO_SARSA && e->S.cb_reps > 1) || greedy ? 6 : 5;
+    if (sp.first) {
+        sp.fused_act = sp.fast && sp.learner && e->hits_ok && pl.fused_act_ok;
+        // env_step_kernel serves the books without a usable hit list itself (act_book in-kernel) -- except in the first step on
+        // lists after they were void, when a late map bit of the step before has voided them again and EVERY book takes the
+        // general path: that step goes through the work list to the general act kernel and env_kernel<64, 2, 2> (either version
+        // is correct for any step).  ... and while MOST books have no usable list (a dense weight vector -- learning.random_init,
+        // a loaded checkpoint: every tile lies on a written weight and no list fits a record): one wave per book in the general
+        // act kernel is far better than a 64-lane wave going through its books one at a time.  The learn kernels hand the same
+        // books back: their list's length of LOB_HINT_LAG steps ago (lob_engine::rest_hint) tells.
+        sp.mostly_general = e->sw.force_general >= 0 ? e->sw.force_general == 1 : e->hint_now > e->B / 16;
+        sp.inline_general = pl.inline_ok && e->steps_on_lists >= 1 && !sp.mostly_general;
+        if (sp.fused_act) e->steps_on_lists++;
+    }
+    if (sp.second && sp.learner && sp.fast) {
+        // (not while the learn kernel hands most books back -- a dense theta: every one of them would go on the list through one counter)
+        sp.acc_fused = pl.acc_fuse_ok && !sp.acc_blocked && e->hint_now <= std::max(1024, e->B / 16);
+        sp.rest_merged = sp.acc_fused && e->sw.rest_merge;
+        if (!sp.rest_merged) {
+            // learn_q_rest_kernel beside the trace kernels: worth it only while books ARE handed back -- an empty launch is
+            // cheaper than the two cross-stream waits
+            if (e->hint_now > 0) e->rest_recent = 64;
+            else if (e->rest_recent > 0) e->rest_recent--;
+            sp.rest_side = pl.rest_side_ok && e->rest_recent > 0;
+        }
+    }
+    sp.registered = sp.second && sp.learner && e->P.sarsa_lanes;
+    return LOB_OK;
+}
+
+// lob_debug_flow, from the step's plan.  Each half counts what it launches: a step abandoned after its first half has counted
+// one of [4]-[6] and nothing else.
+static void count_flow(lob_engine* e, const StepPlan& sp, int half) {
+    if (half == 1) { e->flow[sp.inline_general ? 4 : sp.mostly_general ? 5 : 6]++; return; }
+    e->flow[sp.acc_blocked ? 2 : sp.acc_fused ? 0 : 3]++;
+    if (sp.dense_on) e->flow[7]++;
+    if (sp.rest_side) e->flow[1]++;
+}
+
+// The step words in the host's DevState (cb_par, cb_dense_on; in both halves of a split step).  Slots claimed from here on take
+// a dense id while the update sums per block.  The generations' records of their slots' ids (tr_cbd) are only kept up by
+// accumulate_dense_kernel: whenever the mode comes on (epsilon has fallen below 0.34, lob_set_epsilon), every record is void --
+// the kernels that verified slots meanwhile did not look ids up.  The backtester leaves cb_par as it is.
+static int set_step_words(lob_engine* e, const StepPlan& sp) {
+    if (sp.learner) e->S.cb_par = sp.par;
+    if (sp.dense_on) e->dense_ever = true;
+    if (sp.dense_on && !e->S.cb_dense_on) HIPCHK(hipMemsetAsync(e->S.tr_cbd, 0xff, (size_t)e->B * e->P.trace_gens * 8, e->stream));
+    e->S.cb_dense_on = sp.dense_on;
+    return LOB_OK;
+}
+// ... and the rule that gets them to the claims.  The claims read both words through the device-resident state (cb_claim_finish,
+// lob_learn.h: S.self), which sync_state uploads with both at 0.  So in every learner step that claims combine slots, memo_kernel
+// (`which` 0) or step_words_kernel publishes them before any claim: this launch, the first of the learn half.
+static void publish_step_words(lob_engine* e, const StepPlan& sp, hipStream_t st) {
+    if (sp.fast) launch_memo(e, sp.par, sp.learner ? 0 : 1);  // (learner: S0 under theta_t for the learn kernels; backtester: for the next act)
+    else if (sp.learner && e->P.combine) hipLaunchKernelGGL(step_words_kernel, dim3(1), dim3(1), 0, st, e->S_dev, e->S.cb_par, e->S.cb_dense_on);
+}
+
+// The action half of one group: action selection + performAction
+static int act_half(lob_engine* e, const StepPlan& sp, const StepGroup& gr, int G) {
+    const hipStream_t st = gr.st;
+    const uint32_t* rnd = (const uint32_t*)e->rnd_dev;
+    const bool dq = e->P.algo == LOB_ALGO_DOUBLE_Q;  // (fast && dq: every step without usable hit lists takes the general act kernel over the whole batch)
+    const i32* act_list = e->S.slow_list, *act_n = e->S.slow_n + sp.lpar * 2;
+    // stagger: group 1 starts acting when group 0 has finished acting, so that the
+    // latency-bound env kernel of one group runs beside a gather kernel of the other
+    if (G > 1 && gr.g == 1) HIPCHK(hipStreamWaitEvent(st, e->ev_stagger, 0));
+    if (sp.fused_act) {
+        // The action selection inside the env kernel: env_step_kernel (two trade slots; LOB_ENV_STEP=0: env_kernel<64, 2, 1>),
+        // then, unless it served them itself, the general act kernel for the books it left on the work list and their steps
+        // (env_kernel<64, TM, 2>)
+        count_flow(e, sp, 1);
+        const DevParams* Pd = (const DevParams*)e->P_dev;
+        const bool t2 = e->P.T <= 2;
+        const int nb = e->B, sid = e->step_id;
+        const EnvFuse F1{nullptr, nullptr, sp.lpar, sid - 1, sp.ver}, F2{act_list, act_n, sp.lpar, sid - 1, sp.ver};
+        {
+            TimedLaunch t(e, "env_kernel", st);
+            if (e->plan.env_step) lobk_env_step(st, sp.inline_general, dq, e->plan.half_waves, e->plan.env16, Pd, e->S, nb, sid, sp.par, F1, rnd);
+            else lobk_env_mode(st, t2, 1, Pd, e->S, nb, sid, sp.par, F1);
+        }
+        if (!sp.inline_general) {
+            {
+                TimedLaunch t(e, "act_rest_kernel", st);
+                if (dq) hipLaunchKernelGGL((act_kernel<LOB_ALGO_DOUBLE_Q, true>), dim3(gr.gl), dim3(LOB_BLOCK), 0, st, LOB_PS(e), rnd, 0, 0, e->B, sp.par, act_list, act_n);
+                else hipLaunchKernelGGL((act_kernel<LOB_ALGO_SARSA, true>), dim3(gr.gl), dim3(LOB_BLOCK), 0, st, LOB_PS(e), rnd, 0, 0, e->B, sp.par, act_list, act_n);
+            }
+            TimedLaunch t(e, "env_rest_kernel", st);
+            lobk_env_mode(st, t2, 2, Pd, e->S, nb, sid, sp.par, F2);
+        }
+    } else if (sp.fast && !dq) {
+        {
+            TimedLaunch t(e, "act_kernel", st);
+            if (sp.learner && e->hits_ok && e->sw.light)
+                hipLaunchKernelGGL(act_light_kernel, dim3((gr.nb + LOB_LIGHT_BLOCK - 1) / LOB_LIGHT_BLOCK), dim3(LOB_LIGHT_BLOCK), 0, st, LOB_PS(e), sp.par, sp.lpar, sp.ver, e->step_id - 1);
+            else
+                hipLaunchKernelGGL(act_fast_kernel<LOB_FAST_NB>, dim3(gr.gf), dim3(LOB_FAST_BLOCK), fast_lds_bytes(e->P.cwords4, LOB_FAST_NB, false), st, LOB_PS(e), rnd, sp.mode, sp.par, sp.lpar, sp.ver);
+        }
+        TimedLaunch t(e, "act_rest_kernel", st);
+        hipLaunchKernelGGL((act_kernel<LOB_ALGO_SARSA, true>), dim3(gr.gl), dim3(LOB_BLOCK), 0, st, LOB_PS(e), rnd, sp.mode, 0, e->B, sp.par, act_list, act_n);
+    } else {
+        TimedLaunch t(e, "act_kernel", st);
+        if (dq) hipLaunchKernelGGL((act_kernel<LOB_ALGO_DOUBLE_Q, false>), dim3(gr.gw), dim3(LOB_BLOCK), 0, st, LOB_PS(e), rnd, sp.mode, gr.b0, gr.nb, sp.par, (const i32*)nullptr, (const i32*)nullptr);
+        else hipLaunchKernelGGL((act_kernel<LOB_ALGO_SARSA, false>), dim3(gr.gw), dim3(LOB_BLOCK), 0, st, LOB_PS(e), rnd, sp.mode, gr.b0, gr.nb, sp.par, (const i32*)nullptr, (const i32*)nullptr);
+    }
+    if (G > 1 && gr.g == 0) HIPCHK(hipEventRecord(e->ev_stagger, st));
+    if (!sp.fused_act) {
+        TimedLaunch t(e, "env_kernel", st);
+        launch_env(e, st, (const i32*)nullptr, sp.learner ? 1 : 0, gr.b0, gr.nb, sp.par);
+    }
+    return LOB_OK;
+}
+
+// The learn half of one group: the step words and memo, traces, TD errors
+static int learn_half(lob_engine* e, const StepPlan& sp, const StepGroup& gr) {
+    const hipStream_t st = gr.st;
+    publish_step_words(e, sp, st);
+    if (!sp.learner) return LOB_OK;
+    const uint32_t* rnd = (const uint32_t*)e->rnd_dev;
+    const int algo = e->P.algo, par = sp.par, lpar = sp.lpar, sid = e->step_id;
+    const bool dq = algo == LOB_ALGO_DOUBLE_Q;
+    if (!sp.fast) {
+        TimedLaunch t(e, "learn_kernel", st);
+        if (dq) hipLaunchKernelGGL((learn_kernel<LOB_ALGO_DOUBLE_Q, false>), dim3(gr.gw), dim3(LOB_BLOCK), 0, st, LOB_PS(e), rnd, gr.b0, gr.nb, par, (const i32*)nullptr, (const i32*)nullptr);
+        else if (algo == LOB_ALGO_QLAMBDA) hipLaunchKernelGGL((learn_kernel<LOB_ALGO_QLAMBDA, false>), dim3(gr.gw), dim3(LOB_BLOCK), 0, st, LOB_PS(e), rnd, gr.b0, gr.nb, par, (const i32*)nullptr, (const i32*)nullptr);
+        else hipLaunchKernelGGL((learn_kernel<LOB_ALGO_SARSA, false>), dim3(gr.gw), dim3(LOB_BLOCK), 0, st, LOB_PS(e), rnd, gr.b0, gr.nb, par, (const i32*)nullptr, (const i32*)nullptr);
+        return LOB_OK;
+    }
+    // (the tile registry's entries for the slots that were new in the step before -- the extra blocks of its trace_lane_kernel
+    // and apply_kernel launches -- are read from here on: the dup flags by the light trace step, the rest by trace_lane_kernel)
+    const EnginePlan& pl = e->plan;
+    const int nb = gr.nb;
+    const i32* learn_list = e->S.slow_list + e->B, *learn_n = e->S.slow_n + lpar * 2 + 1;
+    const int acc_fuse = sp.acc_fused ? (sp.rest_merged ? 2 : 1) : 0;
+    const int gt = std::min((4 * LOB_TRACE_OCC / LOB_TRACE_WAVES) * e->n_cus, (nb + LOB_TRACE_WAVES - 1) / LOB_TRACE_WAVES);
+    if (pl.t_light && !pl.fuse) {
+        // a lane per book where the step leaves no older generation behind, the wave-per-book kernel for the rest
+        TimedLaunch t(e, "trace_light_kernel", st);
+        hipLaunchKernelGGL(trace_light_kernel, dim3((nb + LOB_LIGHT_BLOCK - 1) / LOB_LIGHT_BLOCK), dim3(LOB_LIGHT_BLOCK), 0, st, LOB_PS(e), lpar);
+    }
+    auto launch_traces = [&]() {
+        if (pl.fuse) return;
+        TimedLaunch t(e, "trace_kernel", st);
+        if (pl.t_light) hipLaunchKernelGGL((trace_fast_kernel<LOB_ALGO_QLAMBDA, 1>), dim3(gt), dim3(LOB_TRACE_BLOCK), trace_lds_bytes(), st, LOB_PS(e), rnd, par, lpar, sid);
+        else if (algo == LOB_ALGO_QLAMBDA) hipLaunchKernelGGL((trace_fast_kernel<LOB_ALGO_QLAMBDA, 0>), dim3(gt), dim3(LOB_TRACE_BLOCK), trace_lds_bytes(), st, LOB_PS(e), rnd, par, lpar, sid);
+        else if (e->P.sarsa_lanes) {
+            // a lane per generation; the wave-per-book kernel for the books it leaves on the list
+            // (LOB_TS_GRID / LOB_TS_LDS, experiments: fewer, persistent blocks / dynamic LDS to throttle the occupancy -- halving
+            // it costs 28 %, a persistent grid changes nothing: NOTES.md "Round 5")
+            const int ts_full = (nb + LOB_TS_BLOCK / 32 - 1) / (LOB_TS_BLOCK / 32);
+            // (its first LOB_REG_BLOCKS blocks: the tile registry for the memo slots that are new on this step's list)
+            hipLaunchKernelGGL(trace_lane_kernel<LOB_ALGO_SARSA>, dim3((e->sw.ts_grid > 0 ? std::min(e->sw.ts_grid, ts_full) : ts_full) + LOB_REG_BLOCKS), dim3(LOB_TS_BLOCK), e->sw.ts_lds, st,
+                               LOB_PS(e), lpar, sid, 0, rnd, par, e->reg_apar, LOB_REG_BLOCKS);
+            hipLaunchKernelGGL((trace_fast_kernel<LOB_ALGO_SARSA, 1>), dim3(gt), dim3(LOB_TRACE_BLOCK), trace_lds_bytes(), st, LOB_PS(e), rnd, par, lpar, sid);
+        }
+        else hipLaunchKernelGGL((trace_fast_kernel<LOB_ALGO_SARSA, 0>), dim3(gt), dim3(LOB_TRACE_BLOCK), trace_lds_bytes(), st, LOB_PS(e), rnd, par, lpar, sid);
+    };
+    // (SARSA(lambda)'s trace kernels run IN FRONT OF its learn kernels: they mark the new generation's tiles in the
+    // written-weights maps the learn kernels build the hit lists by -- lob_state.h above hl_rec.  The other order exists in
+    // -DLOB_EXPERIMENTS builds only (LOB_SARSA_LEARN_FIRST=1), for the test that shows it to fail.)
+    if (!pl.learn_first) launch_traces();
+    {
+        TimedLaunch t(e, "learn_kernel", st);
+        if (pl.q_lanes) {
+            const bool pair = pl.q_pair;
+            const int gq = pair ? std::min(LOB_QP_OCC * e->n_cus, (nb + LOB_QP_BOOKS - 1) / LOB_QP_BOOKS) : std::min(e->n_cus, (nb + LOB_QL_BLOCK - 1) / LOB_QL_BLOCK);
+            const size_t lds = pair ? qpair_lds_bytes(e->P.cwords4) : qlane_lds_bytes(e->P.cwords4);
+            lobk_learn_q(st, pair, algo, e->P.V == 8, pl.fuse, gq, lds, (const DevParams*)e->P_dev, e->S, rnd, lpar, sp.ver, sid, acc_fuse);
+        } else lobk_learn_q_fast(st, algo, gr.gf, fast_lds_bytes(e->P.cwords4, LOB_FAST_NB, false), (const DevParams*)e->P_dev, e->S, rnd, lpar, sp.ver);
+    }
+    if (!sp.rest_merged) {   // (rest_merged: trace_rest_kernel serves the books handed back too, behind the lane trace kernel)
+        // The books the lane kernels hand back (a list that is empty in most steps, a handful of books in the others).
+        // When trace kernels follow on the main stream (the fused Q(lambda) / double Q flow), this launch may run beside
+        // them on the second stream (StepPlan::rest_side): nothing they do depends on it -- the update kernels wait for both.
+        const hipStream_t rs = sp.rest_side ? e->stream2 : st;
+        if (sp.rest_side) {
+            HIPCHK(hipEventRecord(e->ev_rest_go, st));
+            HIPCHK(hipStreamWaitEvent(e->stream2, e->ev_rest_go, 0));
+        }
+        {
+            TimedLaunch t(e, "learn_rest_kernel", rs);
+            const int rc = report_hint(e, rs, [&](u64* hint_dev, uint32_t hint_tag) {
+                if (dq) hipLaunchKernelGGL(learn_q_rest_kernel<LOB_ALGO_DOUBLE_Q>, dim3(gr.gl), dim3(LOB_BLOCK), 0, rs, LOB_PS(e), rnd, learn_list, learn_n, hint_dev, hint_tag);
+                else if (algo == LOB_ALGO_QLAMBDA) hipLaunchKernelGGL(learn_q_rest_kernel<LOB_ALGO_QLAMBDA>, dim3(gr.gl), dim3(LOB_BLOCK), 0, rs, LOB_PS(e), rnd, learn_list, learn_n, hint_dev, hint_tag);
+                else hipLaunchKernelGGL(learn_q_rest_kernel<LOB_ALGO_SARSA>, dim3(gr.gl), dim3(LOB_BLOCK), 0, rs, LOB_PS(e), rnd, learn_list, learn_n, hint_dev, hint_tag);
+            });
+            if (rc) return rc;
+        }
+        if (sp.rest_side) HIPCHK(hipEventRecord(e->ev_rest_done, e->stream2));
+    }
+    if (pl.learn_first) launch_traces();
+    if (pl.fuse) {
+        TimedLaunch t(e, "trace_kernel", st);
+        // the listed books (their traces survive the step): a lane per generation, then the wave-per-book kernel for
+        // those the lane kernel hands on
+        if (e->P.sarsa_lanes) {
+            // (its first LOB_REG_BLOCKS blocks: the tile registry for the memo slots that are new on this step's list)
+            hipLaunchKernelGGL(trace_lane_kernel<LOB_ALGO_QLAMBDA>, dim3(std::min(4 * e->n_cus, (nb + LOB_TS_BLOCK / 32 - 1) / (LOB_TS_BLOCK / 32)) + LOB_REG_BLOCKS), dim3(LOB_TS_BLOCK), 0, st,
+                               LOB_PS(e), lpar, sid, acc_fuse, rnd, par, e->reg_apar, LOB_REG_BLOCKS);
+        }
+        // (rest_merged: what the lane kernel hands on is served by trace_rest_kernel, in the place of accumulate_kernel)
+        if (!sp.rest_merged) hipLaunchKernelGGL((trace_fast_kernel<LOB_ALGO_QLAMBDA, 2>), dim3(gt), dim3(LOB_TRACE_BLOCK), trace_lds_bytes(), st, LOB_PS(e), rnd, par, lpar, sid);
+    }
+    return LOB_OK;
+}
+
+// The update of every book, on the main stream behind both groups (and the second stream)
+static int update_all(lob_engine* e, const StepPlan& sp) {
+    const uint32_t* rnd = (const uint32_t*)e->rnd_dev;
+    const int par = sp.par, lpar = sp.lpar;
+    if (sp.rest_side) HIPCHK(hipStreamWaitEvent(e->stream, e->ev_rest_done, 0));
+    // model_log: the step's |delta| sums, launched where every stepped book's TD error is final -- behind trace_rest_kernel in
+    // the merged flow (a book the learn kernel handed back still carries Q(s, a) in LHdr::td until that kernel's learn_q_book
+    // has run: ADVICE r5), in front of the update kernels everywhere else
+    auto td_stats = [&]() {
+        if (!(sp.learner && e->model_log)) return;
+        TimedLaunch t(e, "td_stats_kernel");
+        const int nblk = std::min(LOB_ML_BLOCKS, (e->B + 255) / 256), per = (e->B + nblk - 1) / nblk;
+        hipLaunchKernelGGL(td_stats_kernel, dim3(nblk), dim3(256), 0, e->stream, e->S, per);
+        hipLaunchKernelGGL(td_stats_fold_kernel, dim3(1), dim3(64), 0, e->stream, e->S, nblk);
+    };
+    if (!sp.rest_merged) td_stats();
+    if (sp.learner && e->P.combine) {
+        int dense_blocks = 0;
+        {
+            TimedLaunch t(e, "accumulate_kernel");
+            count_flow(e, sp, 2);
+            if (sp.dense_on) {
+                // sums by the slots' dense ids in a direct-indexed LDS array, one block per CU (accumulate_dense_kernel)
+                dense_blocks = std::min(std::min(e->n_cus, LOB_ACD_MAX_BLOCKS), (e->B + 127) / 128);   // (a block takes 128 books per pass)
+                const int bpb = ((e->B + dense_blocks - 1) / dense_blocks + 31) / 32 * 32;
+                dense_blocks = (e->B + bpb - 1) / bpb;
+                hipLaunchKernelGGL(accumulate_dense_kernel, dim3(dense_blocks), dim3(LOB_ACD_BLOCK), acd_lds_bytes(), e->stream, LOB_PS(e), par, e->step_id, bpb);
+                hipLaunchKernelGGL(reduce_dense_kernel, dim3((e->S.cb_ids + 255) / 256, LOB_ACD_GROUPS), dim3(256), 0, e->stream, e->S, dense_blocks);
+            } else if (sp.acc_blocked) {
+                // (batches per block: SARSA(lambda) 80 us with one, 89 with two or four -- its blocks are bound by their LDS insertions, not by what
+                // they send to memory; mostly-greedy Q(lambda) 58 -> 50 us with four)
+                const int nbat = e->sw.acc_batches ? e->sw.acc_batches : (e->P.algo == LOB_ALGO_SARSA ? 1 : std::max(1, std::min(LOB_ACB_K, e->B / (16 * LOB_ACB_BLOCK))));
+                hipLaunchKernelGGL(accumulate_block_kernel, dim3((e->B + LOB_ACB_BLOCK * nbat - 1) / (LOB_ACB_BLOCK * nbat), e->P.trace_kmax), dim3(LOB_ACB_BLOCK), 0, e->stream, LOB_PS(e), par, e->step_id, nbat);
+            } else if (sp.rest_merged) {
+                // the books the learn kernel handed back (TD error + their sums), the books the lane trace kernel handed on (trace
+                // step + their sums) and what the fused accumulation left, in one launch; it reports the hand-back count to the
+                // host as learn_q_rest_kernel does in the other flows
+                const dim3 rg(std::min(e->n_cus, (std::min(e->B, 4096) + LOB_TRACE_WAVES - 1) / LOB_TRACE_WAVES));
+                const int rc = report_hint(e, e->stream, [&](u64* hint_dev, uint32_t hint_tag) {
+                    if (e->P.algo == LOB_ALGO_DOUBLE_Q)
+                        hipLaunchKernelGGL(trace_rest_kernel<LOB_ALGO_DOUBLE_Q>, rg, dim3(LOB_TRACE_BLOCK), trace_lds_bytes(), e->stream, LOB_PS(e), rnd, par, lpar, e->step_id, sp.acc_shift, hint_dev, hint_tag);
+                    else
+                        hipLaunchKernelGGL(trace_rest_kernel<LOB_ALGO_QLAMBDA>, rg, dim3(LOB_TRACE_BLOCK), trace_lds_bytes(), e->stream, LOB_PS(e), rnd, par, lpar, e->step_id, sp.acc_shift, hint_dev, hint_tag);
+                });
+                if (rc) return rc;
+            } else if (sp.acc_fused) {
+                // what the fused accumulation left: a few hundred books (the grid's waves stride over the list)
+                const int waves = (std::min(e->B, 4096) + (64 >> sp.acc_shift) - 1) / (64 >> sp.acc_shift);
+                hipLaunchKernelGGL(accumulate_kernel, dim3((waves + LOB_WAVES_PER_BLOCK - 1) / LOB_WAVES_PER_BLOCK), dim3(LOB_BLOCK), 0, e->stream, LOB_PS(e), par, sp.acc_shift, e->step_id,
+                                   (const i32*)e->S.acc_list, (const i32*)&e->S.acc_list_n[lpar]);
+            } else {
+                const int waves = (e->B + (64 >> sp.acc_shift) - 1) / (64 >> sp.acc_shift);
+                hipLaunchKernelGGL(accumulate_kernel, dim3((waves + LOB_WAVES_PER_BLOCK - 1) / LOB_WAVES_PER_BLOCK), dim3(LOB_BLOCK), 0, e->stream, LOB_PS(e), par, sp.acc_shift, e->step_id,
+                                   (const i32*)nullptr, (const i32*)nullptr);
+            }
+        }
+        if (sp.rest_merged) td_stats();
+        {
+            TimedLaunch t(e, "apply_kernel");
+            const int blocks = e->S.cb_segs;
+            // (dense_blocks -1: no slot has ever been given a dense id -- apply_kernel does not look any up)
+            // (+ the indices the step's registry blocks -- trace_lane_kernel's launch -- found ambiguous, marked in every registered slot)
+            hipLaunchKernelGGL(apply_kernel, dim3(blocks + (sp.registered ? LOB_SCAN_BLOCKS : 0)), dim3(256), 0, e->stream, LOB_PS(e), rnd, par, e->step_id,
+                               e->dense_ever ? dense_blocks : -1, e->reg_apar);
+            if (sp.registered) e->reg_apar ^= 1;
+        }
+    } else if (sp.learner) {
+        TimedLaunch t(e, "update_kernel");
+        hipLaunchKernelGGL(update_kernel, dim3(grid_waves(e->B)), dim3(LOB_BLOCK), 0, e->stream, LOB_PS(e), par, e->step_id);
+    }
+    if (sp.learner && e->P.r_learn) {
+        // R-learning: the average reward rho, after updateQ (rho_kernel, lob_kernels.h)
+        TimedLaunch t(e, "rho_kernel");
+        const int nr = e->P.theta_private ? e->B : 1;
+        hipLaunchKernelGGL(rho_kernel, dim3(grid_waves(e->B)), dim3(LOB_BLOCK), 0, e->stream, e->P, e->S, rnd);
+        hipLaunchKernelGGL(rho_fold_kernel, dim3((nr + 255) / 256), dim3(256), 0, e->stream, e->S, nr);
+    }
+    if (sp.learner) {
+        e->theta_ver++;                          // theta_{t+1}
+        if (e->P.memo) launch_memo(e, par, 1, lpar);   // the same triples again, for the next action selection (+ its list resets)
+    }
+    e->hits_ok = sp.learner && sp.fast;          // learn_q_fast_kernel has left the hit lists of the States the next step acts on
+    maybe_refill_track(e);
+    return LOB_OK;
 }
 
 // `half`: 0 = whole steps; 1 = the first half of ONE learner step (action selection + performAction), 2 = its second half
@@ -1515,307 +1791,29 @@ static int acc_lanes_shift(const lob_engine* e) {
 // no hit list is live (the step's action has consumed the previous step's, the learn kernel builds the next under
 // whatever maps it then finds).
 static int run_steps(lob_engine* e, int32_t n_steps, int mode, int half = 0) {
-    const bool first = half != 2, second = half != 1;
     HIPCHK(hipSetDevice(e->device));
     { int rc = sync_state(e); if (rc) return rc; }
-    const int G = e->B >= 1024 ? e->n_groups : 1;  // small batches: one group (an empty group would be an empty launch)
-    const uint32_t* rnd = (const uint32_t*)e->rnd_dev;
+    const int G = e->plan.groups;
     for (int s = 0; s < n_steps; s++) {
-        // double-buffered list of newly written weights (verdict carry-over, lob_state.h)
-        const int par = mode == 0 ? (first ? (e->td_parity ^= 1) : e->td_parity) : 0;
-        if (first) e->step_id++;
-        if (!e->hits_ok) e->steps_on_lists = 0;
-        const u64 ver = (u64)e->theta_ver;
+        StepPlan sp;
+        { int rc = plan_step(e, mode, half, sp); if (rc) return rc; }
         if (G > 1) {
             HIPCHK(hipEventRecord(e->ev_fork, e->stream));
             HIPCHK(hipStreamWaitEvent(e->stream2, e->ev_fork, 0));
         }
-        const bool fast = e->P.memo != 0;  // (implies one group)
-        if (first) {
-            // the learn kernels' hand-back count of LOB_HINT_LAG learner steps ago (0 until that many have run since the hints were void)
-            e->hint_now = 0;
-            if (fast && mode == 0 && e->rest_hint && e->hint_step >= LOB_HINT_LAG) {
-                // (the latest reporting step that is at least LOB_HINT_LAG steps old)
-                const int hs = (int)(((e->hint_step - LOB_HINT_LAG) / LOB_HINT_EVERY * LOB_HINT_EVERY) % LOB_HINT_RING);
-                HIPCHK(hipEventSynchronize(e->hint_ev[hs]));
-                // (the kernel is done; its store to host memory is a system-scope atomic and carries the launch's tag: wait for that very word)
-                u64 w = *(volatile u64*)(e->rest_hint + hs);
-                for (int spin = 0; (uint32_t)(w >> 32) != e->hint_tags[hs] && spin < (1 << 16); spin++) w = *(volatile u64*)(e->rest_hint + hs);
-                // The count only chooses between two correct paths: a word that has still not arrived (a loaded host, a slow link)
-                // is no reason to abort training -- this step goes by "no book handed back" (ADVICE r5), and is counted
-                // (lob_debug_hint: a test that asserts which path ran must know that the hint decided it)
-                const bool arrived = (uint32_t)(w >> 32) == e->hint_tags[hs];
-                e->hint_now = arrived ? (int)(uint32_t)w : 0;
-                e->hint_reads++;
-                if (!arrived) e->hint_misses++;
-            }
-        }
-        bool rest_pending = false;
-        bool acc_fused = false;  // (this step: see the learn kernel's launch)
-        bool rest_merged = false;  // ... and then trace_rest_kernel instead of trace_fast_kernel<., 2> + accumulate_kernel over its list
-        bool registered = false;   // this step's trace_lane_kernel launch carries the tile registry's blocks (its apply_kernel launch then carries the scan's)
-        bool rest_side_now = false;
-        const bool dq = e->P.algo == LOB_ALGO_DOUBLE_Q;  // (fast && dq: every step without usable hit lists takes the general act kernel over the whole batch)
-        const int lpar = first ? (e->list_par ^= 1) : e->list_par;
-        e->last_par = par;
-        if (mode == 0) e->S.cb_par = par;  // (DevState goes to the kernels by value: the launches below see it)
-        {
-            // slots claimed from here on take a dense id while the update sums per block.  The generations' records of their slots'
-            // ids (tr_cbd) are only kept up by accumulate_dense_kernel: whenever the mode comes on (epsilon has fallen below 0.34,
-            // lob_set_epsilon), every record is void -- the kernels that verified slots meanwhile did not look ids up
-            const int on = e->S.cb_dense && acc_blocked(e) ? 1 : 0;
-            if (on) e->dense_ever = true;
-            if (on && !e->S.cb_dense_on) HIPCHK(hipMemsetAsync(e->S.tr_cbd, 0xff, (size_t)e->B * e->P.trace_gens * 8, e->stream));
-            e->S.cb_dense_on = on;
-        }
+        { int rc = set_step_words(e, sp); if (rc) return rc; }
         for (int g = 0; g < G; g++) {
-            hipStream_t st = g == 0 ? e->stream : e->stream2;
-            const int b0 = (int)((long long)e->B * g / G), nb = (int)((long long)e->B * (g + 1) / G) - b0;
-            const int gw = grid_waves(nb);
-            // the persistent kernels: one 16-wave block per CU; the general kernels then serve the books handed back
-            const int gf = std::min(e->n_cus, (nb + LOB_FAST_WAVES * LOB_FAST_NB - 1) / (LOB_FAST_WAVES * LOB_FAST_NB)), gl = 2 * e->n_cus;
-            const i32* act_list = e->S.slow_list, *learn_list = e->S.slow_list + e->B;
-            const i32* act_n = e->S.slow_n + lpar * 2, *learn_n = e->S.slow_n + lpar * 2 + 1;
-            // stagger: group 1 starts acting when group 0 has finished acting, so that the
-            // latency-bound env kernel of one group runs beside a gather kernel of the other
-            if (first) {
-            if (G > 1 && g == 1) HIPCHK(hipStreamWaitEvent(st, e->ev_stagger, 0));
-            // (batches of 1 024 books and more, env_kernel<64>: the action selection rides in the env kernel -- 4 096 books: 25.0 -> 27.2 M
-            // env-steps/s, 16 384: 65.5 -> 75.8 M)
-            const bool fused_act = fast && mode == 0 && e->hits_ok && e->light && e->fuse_act && e->env_lanes == 0 && (e->B >= 1024 || e->force_fuse_act);
-            if (fused_act) {
-                launch_env_fused(e, st, par, lpar, ver, act_list, act_n, gl);
-            } else if (fast && !dq) {
-                {
-                    TimedLaunch t(e, "act_kernel", st);
-                    if (mode == 0 && e->hits_ok && e->light)
-                        hipLaunchKernelGGL(act_light_kernel, dim3((nb + LOB_LIGHT_BLOCK - 1) / LOB_LIGHT_BLOCK), dim3(LOB_LIGHT_BLOCK), 0, st, LOB_PS(e), par, lpar, ver, e->step_id - 1);
-                    else
-                        hipLaunchKernelGGL(act_fast_kernel<LOB_FAST_NB>, dim3(gf), dim3(LOB_FAST_BLOCK), fast_lds_bytes(e->P.cwords4, LOB_FAST_NB, false), st, LOB_PS(e), rnd, mode, par, lpar, ver);
-                }
-                {
-                    TimedLaunch t(e, "act_rest_kernel", st);
-                    hipLaunchKernelGGL((act_kernel<LOB_ALGO_SARSA, true>), dim3(gl), dim3(LOB_BLOCK), 0, st, LOB_PS(e), rnd, mode, 0, e->B, par, act_list, act_n);
-                }
-            } else {
-                TimedLaunch t(e, "act_kernel", st);
-                if (e->P.algo == LOB_ALGO_DOUBLE_Q) hipLaunchKernelGGL((act_kernel<LOB_ALGO_DOUBLE_Q, false>), dim3(gw), dim3(LOB_BLOCK), 0, st, LOB_PS(e), rnd, mode, b0, nb, par, (const i32*)nullptr, (const i32*)nullptr);
-                else hipLaunchKernelGGL((act_kernel<LOB_ALGO_SARSA, false>), dim3(gw), dim3(LOB_BLOCK), 0, st, LOB_PS(e), rnd, mode, b0, nb, par, (const i32*)nullptr, (const i32*)nullptr);
-            }
-            if (G > 1 && g == 0) HIPCHK(hipEventRecord(e->ev_stagger, st));
-            if (!fused_act) {
-                TimedLaunch t(e, "env_kernel", st);
-                launch_env(e, st, (const i32*)nullptr, mode == 0 ? 1 : 0, b0, nb, par);
-            }
-            }  // first half
-            if (!second) continue;
-            if (fast) launch_memo(e, par, mode == 0 ? 0 : 1);  // learner: S0 under theta_t for learn_kernel; backtester: for the next act
-            // (... and, which 0, the step's cb_par / cb_dense_on into the state's device-resident copy; without a memo launch:)
-            else if (mode == 0 && e->P.combine) hipLaunchKernelGGL(step_words_kernel, dim3(1), dim3(1), 0, st, e->S_dev, e->S.cb_par, e->S.cb_dense_on);
-            // (the tile registry's entries for the slots that were new in the step before -- the extra blocks of its trace_lane_kernel
-            // and apply_kernel launches -- are read from here on: the dup flags by the light trace step, the rest by trace_lane_kernel)
-            if (mode == 0 && fast) {
-                const bool tl = (e->P.algo == LOB_ALGO_QLAMBDA || dq) && e->t_light;
-                // Q(s', .) + TD error: a lane per book once the batch gives every CU a full block of them, else a wave per book
-                const bool lanes = e->q_lanes >= 0 ? e->q_lanes == 1 : nb >= LOB_QL_BLOCK * e->n_cus / 2;
-                // ... and then the lane kernel also takes the trace step of the books it can (those left go on a list for the
-                // wave-per-book trace kernel, which runs AFTER it)
-                const bool fuse = tl && lanes && !e->no_fuse;
-                const int gt = std::min((4 * LOB_TRACE_OCC / LOB_TRACE_WAVES) * e->n_cus, (nb + LOB_TRACE_WAVES - 1) / LOB_TRACE_WAVES);
-                const int sid = e->step_id;
-                if (tl && !fuse) {
-                    // a lane per book where the step leaves no older generation behind, the wave-per-book kernel for the rest
-                    TimedLaunch t(e, "trace_light_kernel", st);
-                    hipLaunchKernelGGL(trace_light_kernel, dim3((nb + LOB_LIGHT_BLOCK - 1) / LOB_LIGHT_BLOCK), dim3(LOB_LIGHT_BLOCK), 0, st, LOB_PS(e), lpar);
-                }
-                auto launch_traces = [&]() {
-                    if (!fuse) {
-                        TimedLaunch t(e, "trace_kernel", st);
-                        if (tl) hipLaunchKernelGGL((trace_fast_kernel<LOB_ALGO_QLAMBDA, 1>), dim3(gt), dim3(LOB_TRACE_BLOCK), trace_lds_bytes(), st, LOB_PS(e), rnd, par, lpar, sid);
-                        else if (e->P.algo == LOB_ALGO_QLAMBDA) hipLaunchKernelGGL((trace_fast_kernel<LOB_ALGO_QLAMBDA, 0>), dim3(gt), dim3(LOB_TRACE_BLOCK), trace_lds_bytes(), st, LOB_PS(e), rnd, par, lpar, sid);
-                        else if (e->P.sarsa_lanes) {
-                            // a lane per generation; the wave-per-book kernel for the books it leaves on the list
-                            // (LOB_TS_GRID / LOB_TS_LDS, experiments: fewer, persistent blocks / dynamic LDS to throttle the occupancy -- halving
-                            // it costs 28 %, a persistent grid changes nothing: NOTES.md "Round 5")
-                            const int ts_full = (nb + LOB_TS_BLOCK / 32 - 1) / (LOB_TS_BLOCK / 32);
-                            // (its first LOB_REG_BLOCKS blocks: the tile registry for the memo slots that are new on this step's list)
-                            registered = true;
-                            hipLaunchKernelGGL(trace_lane_kernel<LOB_ALGO_SARSA>, dim3((e->ts_grid > 0 ? std::min(e->ts_grid, ts_full) : ts_full) + LOB_REG_BLOCKS), dim3(LOB_TS_BLOCK), e->ts_lds, st,
-                                               LOB_PS(e), lpar, sid, 0, rnd, par, e->reg_apar, LOB_REG_BLOCKS);
-                            hipLaunchKernelGGL((trace_fast_kernel<LOB_ALGO_SARSA, 1>), dim3(gt), dim3(LOB_TRACE_BLOCK), trace_lds_bytes(), st, LOB_PS(e), rnd, par, lpar, sid);
-                        }
-                        else hipLaunchKernelGGL((trace_fast_kernel<LOB_ALGO_SARSA, 0>), dim3(gt), dim3(LOB_TRACE_BLOCK), trace_lds_bytes(), st, LOB_PS(e), rnd, par, lpar, sid);
-                    }
-                };
-                const bool learn_first = lobk_experiments() && e->P.exp_learn_first && e->P.algo == LOB_ALGO_SARSA;
-                // (SARSA(lambda)'s trace kernels run IN FRONT OF its learn kernels: they mark the new generation's tiles in the
-                // written-weights maps the learn kernels build the hit lists by -- lob_state.h above hl_rec.  The other order exists in
-                // -DLOB_EXPERIMENTS builds only (LOB_SARSA_LEARN_FIRST=1), for the test that shows it to fail.)
-                if (!learn_first) launch_traces();
-                {
-                    TimedLaunch t(e, "learn_kernel", st);
-                    if (lanes) {
-                        const bool pair = e->q_pair && e->P.M < (1ll << 27) && (!dq || e->dq_pair);  // (its LDS rows hold tile indices in 27 bits)
-                        // the updates added to their slots by this kernel and trace_lane_kernel (lob_state.h acc_list): Q(lambda) while its
-                        // books keep few generations (else accumulate_block_kernel's sums per block win)
-                        acc_fused = fuse && e->acc_fuse && e->P.combine && e->P.sarsa_lanes && (e->P.algo == LOB_ALGO_QLAMBDA || dq) && !acc_blocked(e) && G == 1;
-                        // (not while the learn kernel hands most books back -- a dense theta: every one of them would go on the list
-                        // through one counter; the list's length of a few steps ago, as launch_env_fused reads it)
-                        if (e->hint_now > std::max(1024, e->B / 16)) acc_fused = false;
-                        rest_merged = acc_fused && e->rest_merge;
-                        const int gq = pair ? std::min(LOB_QP_OCC * e->n_cus, (nb + LOB_QP_BOOKS - 1) / LOB_QP_BOOKS) : std::min(e->n_cus, (nb + LOB_QL_BLOCK - 1) / LOB_QL_BLOCK);
-                        const size_t lds = pair ? qpair_lds_bytes(e->P.cwords4) : qlane_lds_bytes(e->P.cwords4);
-                        lobk_learn_q(st, pair, e->P.algo, e->P.V == 8, fuse, gq, lds, (const DevParams*)e->P_dev, e->S, rnd, lpar, ver, sid, acc_fused ? (rest_merged ? 2 : 1) : 0);
-                    } else lobk_learn_q_fast(st, e->P.algo, gf, fast_lds_bytes(e->P.cwords4, LOB_FAST_NB, false), (const DevParams*)e->P_dev, e->S, rnd, lpar, ver);
-                }
-                if (!rest_merged) {   // (rest_merged: trace_rest_kernel serves the books handed back too, behind the lane trace kernel)
-                    // The books the lane kernels hand back (a list that is empty in most steps, a handful of books in the others).
-                    // When trace kernels follow on the main stream (the fused Q(lambda) / double Q flow), this launch runs beside
-                    // them on the second stream: nothing they do depends on it -- the update kernels wait for both.
-                    // (worth it only while books ARE handed back -- an empty launch is cheaper than the two cross-stream waits: the
-                    // kernel reports its list's length through a host-mapped word, read here a few steps late)
-                    if (e->hint_now > 0) e->rest_recent = 64;
-                    else if (e->rest_recent > 0) e->rest_recent--;
-                    const bool side = fuse && e->rest_side && e->rest_recent > 0;
-                    hipStream_t rs = side ? e->stream2 : st;
-                    if (side) {
-                        HIPCHK(hipEventRecord(e->ev_rest_go, st));
-                        HIPCHK(hipStreamWaitEvent(e->stream2, e->ev_rest_go, 0));
-                    }
-                    {
-                        TimedLaunch t(e, "learn_rest_kernel", rs);
-                        const int hs = (int)(e->hint_step % LOB_HINT_RING);
-                        const bool no_hint = e->no_hint;  // (experiment: the hint's store to host memory costs the kernel 3.5 us and the step nothing)
-                        const bool reports = e->rest_hint && !no_hint && e->hint_step % LOB_HINT_EVERY == 0;
-                        u64* hint_dev = reports ? e->rest_hint_dev + hs : nullptr;
-                        const uint32_t hint_tag = (uint32_t)(++e->hint_serial);
-                        if (dq) hipLaunchKernelGGL(learn_q_rest_kernel<LOB_ALGO_DOUBLE_Q>, dim3(gl), dim3(LOB_BLOCK), 0, rs, LOB_PS(e), rnd, learn_list, learn_n, hint_dev, hint_tag);
-                        else if (e->P.algo == LOB_ALGO_QLAMBDA) hipLaunchKernelGGL(learn_q_rest_kernel<LOB_ALGO_QLAMBDA>, dim3(gl), dim3(LOB_BLOCK), 0, rs, LOB_PS(e), rnd, learn_list, learn_n, hint_dev, hint_tag);
-                        else hipLaunchKernelGGL(learn_q_rest_kernel<LOB_ALGO_SARSA>, dim3(gl), dim3(LOB_BLOCK), 0, rs, LOB_PS(e), rnd, learn_list, learn_n, hint_dev, hint_tag);
-                        if (reports) { HIPCHK(hipEventRecord(e->hint_ev[hs], rs)); e->hint_tags[hs] = hint_tag; }
-                        if (e->rest_hint && !no_hint) e->hint_step++;
-                    }
-                    if (side) {
-                        HIPCHK(hipEventRecord(e->ev_rest_done, e->stream2));
-                        rest_pending = true;
-                        rest_side_now = true;
-                    }
-                }
-                if (learn_first) launch_traces();
-                if (fuse) {
-                    TimedLaunch t(e, "trace_kernel", st);
-                    // the listed books (their traces survive the step): a lane per generation, then the wave-per-book kernel for
-                    // those the lane kernel hands on
-                    if (e->P.sarsa_lanes) {
-                        // (its first LOB_REG_BLOCKS blocks: the tile registry for the memo slots that are new on this step's list)
-                        registered = true;
-                        hipLaunchKernelGGL(trace_lane_kernel<LOB_ALGO_QLAMBDA>, dim3(std::min(4 * e->n_cus, (nb + LOB_TS_BLOCK / 32 - 1) / (LOB_TS_BLOCK / 32)) + LOB_REG_BLOCKS), dim3(LOB_TS_BLOCK), 0, st,
-                                           LOB_PS(e), lpar, sid, acc_fused ? (rest_merged ? 2 : 1) : 0, rnd, par, e->reg_apar, LOB_REG_BLOCKS);
-                    }
-                    // (rest_merged: what the lane kernel hands on is served by trace_rest_kernel, in the place of accumulate_kernel below)
-                    if (!rest_merged) hipLaunchKernelGGL((trace_fast_kernel<LOB_ALGO_QLAMBDA, 2>), dim3(gt), dim3(LOB_TRACE_BLOCK), trace_lds_bytes(), st, LOB_PS(e), rnd, par, lpar, sid);
-                }
-            } else if (mode == 0) {
-                TimedLaunch t(e, "learn_kernel", st);
-                if (e->P.algo == LOB_ALGO_DOUBLE_Q) hipLaunchKernelGGL((learn_kernel<LOB_ALGO_DOUBLE_Q, false>), dim3(gw), dim3(LOB_BLOCK), 0, st, LOB_PS(e), rnd, b0, nb, par, (const i32*)nullptr, (const i32*)nullptr);
-                else if (e->P.algo == LOB_ALGO_QLAMBDA) hipLaunchKernelGGL((learn_kernel<LOB_ALGO_QLAMBDA, false>), dim3(gw), dim3(LOB_BLOCK), 0, st, LOB_PS(e), rnd, b0, nb, par, (const i32*)nullptr, (const i32*)nullptr);
-                else hipLaunchKernelGGL((learn_kernel<LOB_ALGO_SARSA, false>), dim3(gw), dim3(LOB_BLOCK), 0, st, LOB_PS(e), rnd, b0, nb, par, (const i32*)nullptr, (const i32*)nullptr);
-            }
+            const StepGroup gr = step_group(e, g, G);
+            if (sp.first) { int rc = act_half(e, sp, gr, G); if (rc) return rc; }
+            if (sp.second) { int rc = learn_half(e, sp, gr); if (rc) return rc; }
         }
         if (G > 1) {
             HIPCHK(hipEventRecord(e->ev_join, e->stream2));
             HIPCHK(hipStreamWaitEvent(e->stream, e->ev_join, 0));
         }
-        if (!second) { e->half_open = true; continue; }
+        if (!sp.second) { e->half_open = true; continue; }
         e->half_open = false;
-        if (rest_pending) { HIPCHK(hipStreamWaitEvent(e->stream, e->ev_rest_done, 0)); rest_pending = false; }
-        // model_log: the step's |delta| sums, launched where every stepped book's TD error is final -- behind trace_rest_kernel in
-        // the merged flow (a book the learn kernel handed back still carries Q(s, a) in LHdr::td until that kernel's learn_q_book
-        // has run: ADVICE r5), in front of the update kernels everywhere else
-        auto td_stats = [&]() {
-            if (!(mode == 0 && e->model_log)) return;
-            TimedLaunch t(e, "td_stats_kernel");
-            const int nblk = std::min(LOB_ML_BLOCKS, (e->B + 255) / 256), per = (e->B + nblk - 1) / nblk;
-            hipLaunchKernelGGL(td_stats_kernel, dim3(nblk), dim3(256), 0, e->stream, e->S, per);
-            hipLaunchKernelGGL(td_stats_fold_kernel, dim3(1), dim3(64), 0, e->stream, e->S, nblk);
-        };
-        if (!rest_merged) td_stats();
-        if (mode == 0 && e->P.combine) {
-            int dense_blocks = 0;
-            {
-                TimedLaunch t(e, "accumulate_kernel");
-                // SARSA(lambda): every book keeps all its generations -- sums per slot inside 1 024-book blocks first.  The same for
-                // Q(lambda) once most actions are greedy (P(greedy) = 1 - eps + eps / 9 > 0.7: more than three live generations per book)
-                e->flow[acc_blocked(e) ? 2 : acc_fused ? 0 : 3]++;
-                if (acc_blocked(e) && e->S.cb_dense) e->flow[7]++;
-                if (rest_side_now) e->flow[1]++;
-                if (acc_blocked(e) && e->S.cb_dense) {
-                    // sums by the slots' dense ids in a direct-indexed LDS array, one block per CU (accumulate_dense_kernel)
-                    dense_blocks = std::min(std::min(e->n_cus, LOB_ACD_MAX_BLOCKS), (e->B + 127) / 128);   // (a block takes 128 books per pass)
-                    const int bpb = ((e->B + dense_blocks - 1) / dense_blocks + 31) / 32 * 32;
-                    dense_blocks = (e->B + bpb - 1) / bpb;
-                    hipLaunchKernelGGL(accumulate_dense_kernel, dim3(dense_blocks), dim3(LOB_ACD_BLOCK), acd_lds_bytes(), e->stream, LOB_PS(e), par, e->step_id, bpb);
-                    hipLaunchKernelGGL(reduce_dense_kernel, dim3((e->S.cb_ids + 255) / 256, LOB_ACD_GROUPS), dim3(256), 0, e->stream, e->S, dense_blocks);
-                } else if (acc_blocked(e)) {
-                    // (batches per block: SARSA(lambda) 80 us with one, 89 with two or four -- its blocks are bound by their LDS insertions, not by what
-                    // they send to memory; mostly-greedy Q(lambda) 58 -> 50 us with four)
-                    const int nbat = e->acc_batches_set ? e->acc_batches : (e->P.algo == LOB_ALGO_SARSA ? 1 : std::max(1, std::min(e->acc_batches, e->B / (16 * LOB_ACB_BLOCK))));
-                    hipLaunchKernelGGL(accumulate_block_kernel, dim3((e->B + LOB_ACB_BLOCK * nbat - 1) / (LOB_ACB_BLOCK * nbat), e->P.trace_kmax), dim3(LOB_ACB_BLOCK), 0, e->stream, LOB_PS(e), par, e->step_id, nbat);
-                } else if (rest_merged) {
-                    // the books the learn kernel handed back (TD error + their sums), the books the lane trace kernel handed on (trace
-                    // step + their sums) and what the fused accumulation left, in one launch; it reports the hand-back count to the
-                    // host as learn_q_rest_kernel does in the other flows
-                    const int hs = (int)(e->hint_step % LOB_HINT_RING);
-                    const bool reports = e->rest_hint && !e->no_hint && e->hint_step % LOB_HINT_EVERY == 0;
-                    u64* hint_dev = reports ? e->rest_hint_dev + hs : nullptr;
-                    const uint32_t hint_tag = (uint32_t)(++e->hint_serial);
-                    const dim3 rg(std::min(e->n_cus, (std::min(e->B, 4096) + LOB_TRACE_WAVES - 1) / LOB_TRACE_WAVES));
-                    if (e->P.algo == LOB_ALGO_DOUBLE_Q)
-                        hipLaunchKernelGGL(trace_rest_kernel<LOB_ALGO_DOUBLE_Q>, rg, dim3(LOB_TRACE_BLOCK), trace_lds_bytes(), e->stream, LOB_PS(e), rnd, par, lpar, e->step_id, acc_lanes_shift(e), hint_dev, hint_tag);
-                    else
-                        hipLaunchKernelGGL(trace_rest_kernel<LOB_ALGO_QLAMBDA>, rg, dim3(LOB_TRACE_BLOCK), trace_lds_bytes(), e->stream, LOB_PS(e), rnd, par, lpar, e->step_id, acc_lanes_shift(e), hint_dev, hint_tag);
-                    if (reports) { HIPCHK(hipEventRecord(e->hint_ev[hs], e->stream)); e->hint_tags[hs] = hint_tag; }
-                    if (e->rest_hint && !e->no_hint) e->hint_step++;
-                } else if (acc_fused) {
-                    // what the fused accumulation left: a few hundred books (the grid's waves stride over the list)
-                    const int sh = acc_lanes_shift(e);
-                    const int waves = (std::min(e->B, 4096) + (64 >> sh) - 1) / (64 >> sh);
-                    hipLaunchKernelGGL(accumulate_kernel, dim3((waves + LOB_WAVES_PER_BLOCK - 1) / LOB_WAVES_PER_BLOCK), dim3(LOB_BLOCK), 0, e->stream, LOB_PS(e), par, sh, e->step_id,
-                                       (const i32*)e->S.acc_list, (const i32*)&e->S.acc_list_n[lpar]);
-                } else {
-                    const int sh = acc_lanes_shift(e);
-                    const int waves = (e->B + (64 >> sh) - 1) / (64 >> sh);
-                    hipLaunchKernelGGL(accumulate_kernel, dim3((waves + LOB_WAVES_PER_BLOCK - 1) / LOB_WAVES_PER_BLOCK), dim3(LOB_BLOCK), 0, e->stream, LOB_PS(e), par, sh, e->step_id,
-                                       (const i32*)nullptr, (const i32*)nullptr);
-                }
-            }
-            if (rest_merged) td_stats();
-            {
-                TimedLaunch t(e, "apply_kernel");
-                const int blocks = e->S.cb_segs;
-                // (dense_blocks -1: no slot has ever been given a dense id -- apply_kernel does not look any up)
-                // (+ the indices the step's registry blocks -- trace_lane_kernel's launch -- found ambiguous, marked in every registered slot)
-                hipLaunchKernelGGL(apply_kernel, dim3(blocks + (registered ? LOB_SCAN_BLOCKS : 0)), dim3(256), 0, e->stream, LOB_PS(e), rnd, par, e->step_id,
-                                   e->dense_ever ? dense_blocks : -1, e->reg_apar);
-                if (registered) e->reg_apar ^= 1;
-            }
-        } else if (mode == 0) {
-            TimedLaunch t(e, "update_kernel");
-            hipLaunchKernelGGL(update_kernel, dim3(grid_waves(e->B)), dim3(LOB_BLOCK), 0, e->stream, LOB_PS(e), par, e->step_id);
-        }
-        if (mode == 0 && e->P.r_learn) {
-            // R-learning: the average reward rho, after updateQ (rho_kernel, lob_kernels.h)
-            TimedLaunch t(e, "rho_kernel");
-            const int nr = e->P.theta_private ? e->B : 1;
-            hipLaunchKernelGGL(rho_kernel, dim3(grid_waves(e->B)), dim3(LOB_BLOCK), 0, e->stream, e->P, e->S, rnd);
-            hipLaunchKernelGGL(rho_fold_kernel, dim3((nr + 255) / 256), dim3(256), 0, e->stream, e->S, nr);
-        }
-        if (mode == 0) {
-            e->theta_ver++;                          // theta_{t+1}
-            if (e->P.memo) launch_memo(e, par, 1, lpar);   // the same triples again, for the next action selection (+ its list resets)
-        }
-        e->hits_ok = mode == 0 && fast;              // learn_q_fast_kernel has left the hit lists of the States the next step acts on
-        maybe_refill_track(e);
+        { int rc = update_all(e, sp); if (rc) return rc; }
     }
     HIPCHK(hipGetLastError());
     return LOB_OK;
@@ -1832,10 +1830,10 @@ int lob_td_step_begin(lob_engine* e) {
     int rc = need_reset(e, "lob_td_step_begin");
     if (rc) return rc;
     if (e->half_open) { lob_set_error("lob_td_step_begin: the previous step has not been ended"); return LOB_ESTATE; }
-    if (e->B >= 1024 && e->n_groups > 1) { lob_set_error("lob_td_step_begin: not with two book groups (LOB_GROUPS=2)"); return LOB_ESTATE; }
+    if (e->plan.groups > 1) { lob_set_error("lob_td_step_begin: not with two book groups (LOB_GROUPS=2)"); return LOB_ESTATE; }
     return run_steps(e, 1, 0, 1);
 }
-int lob_td_split_supported(lob_engine* e) { return e && !(e->B >= 1024 && e->n_groups > 1) ? 1 : 0; }
+int lob_td_split_supported(lob_engine* e) { return e && e->plan.groups == 1 ? 1 : 0; }
 int lob_td_step_end(lob_engine* e) {
     int rc = need_reset(e, "lob_td_step_end");
     if (rc) return rc;
@@ -2177,7 +2175,7 @@ int lob_delta_sparse_maps(lob_engine* e, int32_t world, uint32_t** dev_own, uint
         if (rc != LOB_OK) return rc;
         // (the first fixed count: a 64th of the table, 4 096 .. 262 144 entries; LOB_SPX_COUNT: the tests' small one)
         e->spx_fixed = std::max<int64_t>(4096, std::min<int64_t>(1 << 18, e->P.M / 64));
-        if (const char* g = getenv("LOB_SPX_COUNT")) { const long long v = atoll(g); if (v >= 64) e->spx_fixed = v; }
+        if (e->sw.spx_count) e->spx_fixed = e->sw.spx_count;
         e->spx_fixed = std::min<int64_t>(e->spx_fixed, e->P.M);
     }
     // every buffer of the exchange exists before its first collective starts (lob_theta_allreduce calls this once BEFORE the ranks

@@ -390,6 +390,10 @@ __global__ void __launch_bounds__(64, EnvStepOcc<LANES>::waves) env_step_kernel(
 // The arithmetic is env_step_kernel's, call for call (the row-consuming routines are templates over the row type).  One weight
 // vector, two trade slots per record.
 #define LOB_ENV16_BOOKS 4
+// (its layout: a hit list gathered in three loads of 16 lanes, the deepest record in a 64-word LDS row -- EnginePlan::env16 also
+// checks the engine's own depth and record width)
+static_assert(LOB_HL_MAX <= 48, "env_step16_kernel gathers a hit list in three 16-lane loads");
+static_assert(LOB_MAX_DEPTH <= 12, "env_step16_kernel holds a book's record in one 64-word LDS row");
 template <bool INLINE_GENERAL>
 __global__ void __launch_bounds__(64) env_step16_kernel(const DevParams* __restrict__ Pp, const DevState* __restrict__ Sp, int step_id, int par, EnvFuse F,
                                                         const uint32_t* __restrict__ rnd_g) {
