@@ -356,6 +356,52 @@ int lob_clear_inventory(lob_engine* e);
 int lob_get_book(lob_engine* e, int32_t book, lob_book_dump* out);
 int lob_get_books(lob_engine* e, int32_t first, int32_t n, lob_book_dump* out);
 
+/* ---- episode statistics of the whole batch ---------------------------------
+ * What the reference logs about ONE environment after an episode -- the `training_log` row of Runner::RunEpisode
+ * (src/experiment/serial.cpp:81-88: getEpisodeReward, getEpisodePnL, total_ticks), Base::writeStats and getTotalTransactions
+ * (src/environment/base.cpp:458-473), the test loop's console line `Rwd, Rho, Pnl, nTr, Ppt` per day
+ * (src/main.cpp:215-239) -- reduced over the books of the engine ON THE DEVICE: count, sum, sum of squares, extremes and
+ * the books that hold them, for the whole engine and, with a day library, for the books playing each day.  One record of
+ * 408 bytes per group comes back instead of one lob_book_dump per book.
+ *   Every per-book value is exactly what lob_get_books reports for that book at that moment (episode_reward, episode_pnl,
+ * episode_bandh, total_ticks, ask_transactions + bid_transactions + market_buys + market_sells, market_buys + market_sells,
+ * ticks_with_position; n_live / n_terminal / n_out_of_data count the dump's `terminal` 0 / 1 / 2).  LOB_STATF_RHO is the
+ * IEEE f64 quotient episode_reward / total_ticks of each book (Base::getMeanEpisodeReward); a book with total_ticks == 0
+ * (the reference would print 0/0) is left out of RHO and of n_rho.  A NaN value goes into sum and sumsq as IEEE addition
+ * takes it and is passed over by min / max (every comparison with it is false).
+ *   lob_episode_stats: out[0] is the whole engine (group -1).  by_day != 0 on a day library: out[1 + d] is library day d
+ * for EVERY day of the library, *n_out = 1 + n_days; a day nobody plays comes back as the identity record (n_books 0,
+ * sums 0, min +inf / INT64_MAX, max -inf / INT64_MIN, argmin = argmax = -1).  argmin / argmax are GLOBAL book ids
+ * (book_id_offset + b); ties go to the lowest id.  Two calls on the same state, and two engines that ran the same run,
+ * return bit-identical records (the order of the f64 additions is fixed: DESIGN.md 7b).  Valid whenever lob_get_books is
+ * meaningful: after the first lob_reset, mid-episode (n_live > 0), after lob_clear_inventory.  It is enqueued on the
+ * engine's stream, waits once for its own result and changes no engine state.  LOB_ESTATE: before the first lob_reset,
+ * between lob_td_step_begin and lob_td_step_end, by_day without an episode on a day library; LOB_EINVAL: a NULL argument,
+ * or cap < *n_out (with *n_out set, so that the caller can size its buffer).
+ *   lob_episode_stats_merge (host only): adds `from` into `into` -- counts, sums and sums of squares add, min / max keep
+ * the lower id on a tie, `group` is kept where both agree and becomes -1 otherwise.  The identity record is its neutral
+ * element; it is how a multi-GPU caller puts the ranks' records together. */
+#define LOB_STATF_REWARD 0   /* episode_reward                       (Base::getEpisodeReward)     */
+#define LOB_STATF_RHO    1   /* episode_reward / total_ticks         (Base::getMeanEpisodeReward) */
+#define LOB_STATF_PNL    2   /* episode_pnl                                                       */
+#define LOB_STATF_BANDH  3   /* episode_bandh                                                     */
+#define LOB_STATI_STEPS          0   /* total_ticks                                               */
+#define LOB_STATI_TRANSACTIONS   1   /* Base::getTotalTransactions (base.cpp:469-473)             */
+#define LOB_STATI_MARKET_ORDERS  2   /* market_buys + market_sells                                */
+#define LOB_STATI_TICKS_POSITION 3   /* ticks_with_position                                       */
+typedef struct lob_stat_f64 { double sum, sumsq, min, max; int64_t argmin, argmax; } lob_stat_f64;
+typedef struct lob_stat_i64 { int64_t sum, sumsq, min, max; int64_t argmin, argmax; } lob_stat_i64;
+typedef struct lob_episode_record {
+    int32_t group;                  /* -1: every book of the engine; d >= 0: the books playing library day d */
+    int32_t n_books;                /* books in the group */
+    int32_t n_live, n_terminal, n_out_of_data;   /* by lob_get_terminal's 0 / 1 / 2; they add up to n_books */
+    int32_t n_rho;                  /* books with total_ticks > 0: the only ones LOB_STATF_RHO counts */
+    lob_stat_f64 f[4];              /* LOB_STATF_* */
+    lob_stat_i64 i[4];              /* LOB_STATI_* */
+} lob_episode_record;   /* (not lob_episode_stats: in C a typedef and a function cannot share a name) */
+int lob_episode_stats(lob_engine* e, int32_t by_day, lob_episode_record* out, int32_t cap, int32_t* n_out);
+void lob_episode_stats_merge(lob_episode_record* into, const lob_episode_record* from);
+
 /* ---- learner interface (rl::Agent, include/rl/agent.h:48-77) ------------- */
 
 /* `n_steps` x Learner::_step (src/experiment/serial.cpp:53-70) for every live

@@ -104,6 +104,27 @@ class BookDump(C.Structure):
     ]
 
 
+# lob_episode_stats: the quantities of EpisodeStats.f / .i, in array order (LOB_STATF_* / LOB_STATI_*)
+STATF_REWARD, STATF_RHO, STATF_PNL, STATF_BANDH = 0, 1, 2, 3
+STATI_STEPS, STATI_TRANSACTIONS, STATI_MARKET_ORDERS, STATI_TICKS_POSITION = 0, 1, 2, 3
+
+
+class StatF64(C.Structure):
+    _fields_ = [("sum", C.c_double), ("sumsq", C.c_double), ("min", C.c_double), ("max", C.c_double),
+                ("argmin", C.c_int64), ("argmax", C.c_int64)]
+
+
+class StatI64(C.Structure):
+    _fields_ = [("sum", C.c_int64), ("sumsq", C.c_int64), ("min", C.c_int64), ("max", C.c_int64),
+                ("argmin", C.c_int64), ("argmax", C.c_int64)]
+
+
+class EpisodeStats(C.Structure):
+    """lob_episode_record: one group's record of lob_episode_stats."""
+    _fields_ = [("group", C.c_int32), ("n_books", C.c_int32), ("n_live", C.c_int32), ("n_terminal", C.c_int32),
+                ("n_out_of_data", C.c_int32), ("n_rho", C.c_int32), ("f", StatF64 * 4), ("i", StatI64 * 4)]
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LOB_ENGINE_LIB: an experiment build of the same library (tools/exp_prof.py, tools/exp_variants.sh)
 LIB_PATH = os.environ.get("LOB_ENGINE_LIB") or os.path.join(_HERE, "csrc", "liblob_engine.so")
@@ -164,6 +185,8 @@ def load():
         "lob_clear_inventory": (C.c_int, [vp]),
         "lob_get_book": (C.c_int, [vp, C.c_int32, P(BookDump)]),
         "lob_get_books": (C.c_int, [vp, C.c_int32, C.c_int32, vp]),
+        "lob_episode_stats": (C.c_int, [vp, C.c_int32, vp, C.c_int32, P(C.c_int32)]),
+        "lob_episode_stats_merge": (None, [vp, vp]),
         "lob_td_step": (C.c_int, [vp, C.c_int32]),
         "lob_td_step_begin": (C.c_int, [vp]),
         "lob_td_split_supported": (C.c_int, [vp]),

@@ -1,7 +1,7 @@
 // Host side of the C ABI (include/lob_engine.h): device memory management,
 // kernel launches on one HIP stream, HIP-event kernel timing.  gfx950 only;
-// there is no CPU execution path in this file.  (One of the library's four translation units, lob_launch.h: the environment,
-// pre-pass and fast learner kernels are compiled in lob_tu_env.hip / lob_tu_prepass.hip / lob_tu_learn.hip.)
+// there is no CPU execution path in this file.  (One of the library's five translation units, lob_launch.h: the environment,
+// pre-pass, fast learner and episode-statistics kernels are compiled in lob_tu_env.hip / lob_tu_prepass.hip / lob_tu_learn.hip / lob_tu_stats.hip.)
 #define LOB_TU_SPLIT 1
 #define LOB_TU_MAIN 1
 #include <hip/hip_runtime.h>
@@ -200,6 +200,8 @@ struct lob_engine {
     i64* cnt_sum = nullptr;     // the striped device counters added up (read_counters)
     lob_book_dump* dump_dev = nullptr;
     int dump_cap = 0;
+    lob_episode_record* stats_dev = nullptr;   // lob_episode_stats: [stats_cap] result records, then the blocks' partial records
+    size_t stats_cap = 0;
     bool have_events = false, was_reset = false;
     bool episode_open = false;  // a pre-pass ran and its window sums have not been rolled back to the stop point yet
     bool model_log = false;     // lob_model_log_enable: the step sums |delta| (td_stats_kernel)
@@ -769,6 +771,7 @@ void lob_destroy(lob_engine* e) {
     free_days(e);
     if (e->track_dev) hipFree(e->track_dev);
     if (e->dump_dev) hipFree(e->dump_dev);
+    if (e->stats_dev) hipFree(e->stats_dev);
     if (e->spx_gather) hipFree(e->spx_gather);
     if (e->spx_ev) hipEventDestroy(e->spx_ev);
     if (e->spx_total_host) hipHostFree(e->spx_total_host);
@@ -1406,6 +1409,38 @@ int lob_get_books(lob_engine* e, int32_t first, int32_t n, lob_book_dump* out) {
     return LOB_OK;
 }
 int lob_get_book(lob_engine* e, int32_t book, lob_book_dump* out) { return lob_get_books(e, book, 1, out); }
+
+// The batch's episode statistics, reduced on the device (lob_kernels.h episode_stats_partial_kernel): the kernels get the few field
+// arrays they read as arguments; n_out records come back.  Reads only.
+int lob_episode_stats(lob_engine* e, int32_t by_day, lob_episode_record* out, int32_t cap, int32_t* n_out) {
+    if (!e || !out || !n_out) { lob_set_error("lob_episode_stats: NULL argument"); return LOB_EINVAL; }
+    int rc = need_reset(e, "lob_episode_stats");
+    if (rc) return rc;
+    if ((rc = not_mid_step(e, "lob_episode_stats"))) return rc;
+    if (by_day && (!e->lib || e->lib_cur < 0)) { lob_set_error("lob_episode_stats: by_day without an episode on a day library (lob_load_days, a selection, lob_reset)"); return LOB_ESTATE; }
+    const int n = by_day ? 1 + e->lib_days : 1;
+    *n_out = n;
+    if (cap < n) { lob_set_error("lob_episode_stats: " + std::to_string(n) + " records, room for " + std::to_string(cap)); return LOB_EINVAL; }
+    HIPCHK(hipSetDevice(e->device));
+    const size_t need = (size_t)n * (1 + (size_t)lobk_stats_chunks(e->B));
+    if (e->stats_cap < need) {
+        if (e->stats_dev) hipFree(e->stats_dev);
+        e->stats_dev = nullptr; e->stats_cap = 0;
+        HIPCHK(hipMalloc((void**)&e->stats_dev, need * sizeof(lob_episode_record)));
+        e->stats_cap = need;
+    }
+    StatsSrc s;
+    s.ep_reward = e->S.ep_reward; s.ep_pnl = e->S.ep_pnl; s.ep_bandh = e->S.ep_bandh;
+    s.total_ticks = e->S.total_ticks; s.market_buys = e->S.market_buys; s.market_sells = e->S.market_sells;
+    s.done = e->S.done; s.time_ms = e->S.time_ms; s.ntr_snap = e->S.ntr_snap; s.tick_pos = e->S.tick_pos;
+    s.day = by_day ? e->lib_day[e->lib_cur] : nullptr;
+    s.open_ms = e->P.open_ms; s.close_ms = e->P.close_ms; s.book_id_offset = e->P.book_id_offset; s.B = e->B;
+    lobk_episode_stats(e->stream, s, n, e->stats_dev + n, e->stats_dev);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, e->stats_dev, (size_t)n * sizeof(lob_episode_record), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return LOB_OK;
+}
 
 // One env-step of every book (run_steps).  The books are split into EnginePlan::groups contiguous groups, each running its action
 // half (act -> env) and its learn half (memo, traces, TD errors) on its own stream; both groups only READ theta, so the

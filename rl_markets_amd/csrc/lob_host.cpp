@@ -17,6 +17,7 @@
 
 #include "lob_stream.h"
 #include "lob_internal.h"
+#include "lob_stats.h"
 
 static thread_local std::string g_err;
 void lob_set_error(const std::string& s) { g_err = s; }
@@ -63,6 +64,11 @@ extern "C" {
 
 int lob_abi_version(void) { return LOB_ABI_VERSION; }
 const char* lob_last_error(void) { return g_err.c_str(); }
+
+// the record arithmetic of the reduction kernels themselves (lob_stats.h)
+void lob_episode_stats_merge(lob_episode_record* into, const lob_episode_record* from) {
+    if (into && from) stats_merge(*into, *from);
+}
 
 
 int lob_market_preset(const char* ticker, lob_market* out) {

@@ -15,16 +15,23 @@
 #include "lob_state.h"
 #include "lob_stream.h"
 #include "lob_launch.h"
+#include "lob_stats.h"
 
-// The engine library is built from four translation units (lob_launch.h).  The kernel TEMPLATES of these headers are only
+// The engine library is built from five translation units (lob_launch.h).  The kernel TEMPLATES of these headers are only
 // compiled where they are launched; the plain kernels are compiled in the unit that launches them: LOB_TU_SPLIT + one of
-// LOB_TU_MAIN / LOB_TU_ENV / LOB_TU_PREPASS / LOB_TU_LEARN says which unit this is (neither: one unit holds everything, as the
+// LOB_TU_MAIN / LOB_TU_ENV / LOB_TU_PREPASS / LOB_TU_LEARN / LOB_TU_STATS says which unit this is (neither: one unit holds everything, as the
 // experiment builds of tools/ and the host-side tests of the device headers do).
 #if !defined(LOB_TU_SPLIT)
 #define LOB_IN_MAIN 1
 #define LOB_IN_ENV 1
 #define LOB_IN_PREPASS 1
+#define LOB_IN_STATS 1
 #else
+#if defined(LOB_TU_STATS)
+#define LOB_IN_STATS 1
+#else
+#define LOB_IN_STATS 0
+#endif
 #if defined(LOB_TU_MAIN)
 #define LOB_IN_MAIN 1
 #else
@@ -2787,6 +2794,91 @@ __global__ void dump_kernel(const DevParams* __restrict__ Pp, DevState S, int fi
     }
     d.n_traces = n_tr;
     out[t] = d;
+}
+#endif
+
+// ---- episode statistics (lob_episode_stats, include/lob_engine.h) ----------------------------------------
+// A reduction over the books, grouped by the day each book plays, of what dump_kernel reports per book -- read straight from the
+// environment field arrays (the pointers arrive as arguments: StatsSrc, lob_launch.h), no DevState, no dump.  Group g = blockIdx.y:
+// 0 is the whole engine, 1 + d the books whose day word is d.  Block (c, g) takes the books of chunk c = [c * LOB_STATS_CHUNK,
+// (c + 1) * LOB_STATS_CHUNK) that belong to g -- it scans the chunk's day words (4 B per book, out of L2 for every group after
+// the first) and loads the fields of its own books only -- and leaves ONE partial record; episode_stats_final_kernel puts a
+// group's partials together.  No floating-point atomics and no same-address tail (NOTES.md "Round 6"), no LDS sized by the number of
+// days: the same path serves one day and thousands.
+//   The order of the f64 additions is fixed by (book index, LOB_STATS_CHUNK) alone:
+//     thread t of a block adds its books c * CHUNK + t, + 256, + 512, ... in that order (coalesced loads);
+//     a wave folds its 64 lanes by the tree lane l += lane l + 32, 16, 8, 4, 2, 1 (stats_wave_fold);
+//     thread 0 adds the block's four wave results in wave order;
+//     the final kernel's lane l adds the partials of chunks l, l + 64, ... in that order, then the same tree over the lanes.
+//   Counts, integer sums and the extremes (value, lowest id) do not depend on any order.
+#if LOB_IN_STATS
+__device__ inline void stats_wave_fold(lob_episode_record& r) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        lob_episode_record o;
+        o.group = r.group;
+        o.n_books = __shfl_down(r.n_books, off); o.n_live = __shfl_down(r.n_live, off); o.n_terminal = __shfl_down(r.n_terminal, off);
+        o.n_out_of_data = __shfl_down(r.n_out_of_data, off); o.n_rho = __shfl_down(r.n_rho, off);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            o.f[k].sum = __shfl_down(r.f[k].sum, off); o.f[k].sumsq = __shfl_down(r.f[k].sumsq, off);
+            o.f[k].min = __shfl_down(r.f[k].min, off); o.f[k].max = __shfl_down(r.f[k].max, off);
+            o.f[k].argmin = __shfl_down((long long)r.f[k].argmin, off); o.f[k].argmax = __shfl_down((long long)r.f[k].argmax, off);
+            o.i[k].sum = __shfl_down((long long)r.i[k].sum, off); o.i[k].sumsq = __shfl_down((long long)r.i[k].sumsq, off);
+            o.i[k].min = __shfl_down((long long)r.i[k].min, off); o.i[k].max = __shfl_down((long long)r.i[k].max, off);
+            o.i[k].argmin = __shfl_down((long long)r.i[k].argmin, off); o.i[k].argmax = __shfl_down((long long)r.i[k].argmax, off);
+        }
+        stats_merge(r, o);   // lanes whose partner is past the wave fold themselves in: their results are not used
+    }
+}
+
+__global__ __launch_bounds__(LOB_STATS_BLOCK) void episode_stats_partial_kernel(StatsSrc s, int n_chunks, lob_episode_record* __restrict__ partial) {
+    __shared__ lob_episode_record wave_out[LOB_STATS_BLOCK / 64];
+    const int g = blockIdx.y, c = blockIdx.x, group = g - 1;
+    lob_episode_record r;
+    stats_identity(r, group);
+    const int b_end = min(s.B, (c + 1) * LOB_STATS_CHUNK);
+    for (int b = c * LOB_STATS_CHUNK + threadIdx.x; b < b_end; b += LOB_STATS_BLOCK) {
+        if (g > 0 && s.day[b] != group) continue;
+        const i64 id = (i64)(s.book_id_offset + (u64)b);
+        // the values as dump_kernel derives them
+        const i32 done = s.done[b], time_ms = s.time_ms[b];
+        const bool open = ((i64)time_ms > s.open_ms + 30 * 60000LL) && ((i64)time_ms < s.close_ms - 30 * 60000LL);   // is_open (lob_env.h)
+        const int terminal = done == 2 ? 2 : (open ? 0 : 1);
+        const i32 total_ticks = s.total_ticks[b], market_buys = s.market_buys[b], market_sells = s.market_sells[b];
+        const i64 ntr_snap = s.ntr_snap[b], tick_pos = s.tick_pos[b];
+        const i32 ask_transactions = (i32)(uint32_t)ntr_snap, bid_transactions = (i32)(uint32_t)(ntr_snap >> 32);
+        const i32 ticks_with_position = (i32)(uint32_t)tick_pos + (i32)(uint32_t)(tick_pos >> 32);
+        const f64 reward = s.ep_reward[b];
+        r.n_books++;
+        r.n_live += terminal == 0; r.n_terminal += terminal == 1; r.n_out_of_data += terminal == 2;
+        stats_add(r.f[LOB_STATF_REWARD], reward, id);
+        if (total_ticks > 0) { r.n_rho++; stats_add(r.f[LOB_STATF_RHO], reward / (f64)total_ticks, id); }
+        stats_add(r.f[LOB_STATF_PNL], s.ep_pnl[b], id);
+        stats_add(r.f[LOB_STATF_BANDH], s.ep_bandh[b], id);
+        stats_add(r.i[LOB_STATI_STEPS], (i64)total_ticks, id);
+        stats_add(r.i[LOB_STATI_TRANSACTIONS], (i64)ask_transactions + bid_transactions + market_buys + market_sells, id);
+        stats_add(r.i[LOB_STATI_MARKET_ORDERS], (i64)market_buys + market_sells, id);
+        stats_add(r.i[LOB_STATI_TICKS_POSITION], (i64)ticks_with_position, id);
+    }
+    stats_wave_fold(r);
+    if ((threadIdx.x & 63) == 0) wave_out[threadIdx.x >> 6] = r;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < LOB_STATS_BLOCK / 64; w++) stats_merge(r, wave_out[w]);
+        r.group = group;
+        partial[(size_t)g * n_chunks + c] = r;
+    }
+}
+
+// One wave per group: out[g] = the group's n_chunks partial records, in chunk order (above)
+__global__ __launch_bounds__(64) void episode_stats_final_kernel(const lob_episode_record* __restrict__ partial, int n_chunks, lob_episode_record* __restrict__ out) {
+    const int g = blockIdx.x, group = g - 1;
+    lob_episode_record r;
+    stats_identity(r, group);
+    for (int c = threadIdx.x; c < n_chunks; c += 64) stats_merge(r, partial[(size_t)g * n_chunks + c]);
+    stats_wave_fold(r);
+    if (threadIdx.x == 0) { r.group = group; out[g] = r; }
 }
 #endif
 

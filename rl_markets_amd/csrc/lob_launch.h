@@ -1,6 +1,6 @@
-// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is four
+// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is five
 // .hip files built in parallel: lob_engine.hip -- the C ABI's host side and the update / memo / trace kernels --, lob_tu_env.hip,
-// lob_tu_prepass.hip, lob_tu_learn.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
+// lob_tu_prepass.hip, lob_tu_learn.hip, lob_tu_stats.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
 // lob_engine.hip used when it held the launches itself.  Kernels measured and lost (NOTES.md "Round 4") are only compiled with
 // -DLOB_EXPERIMENTS (tools/exp_variants.sh); a product build answers LOB_EXPERIMENTS-only requests with the product kernel.
 #ifndef LOB_LAUNCH_H
@@ -42,6 +42,24 @@ void lobk_days_draw(hipStream_t st, int B, u64 first_book, int mode, int first, 
 void lobk_reset(hipStream_t st, int lanes, bool t2, bool roles, const DevParams* Pd, const DevState& S);
 void lobk_prepass_extend(hipStream_t st, bool t2, bool roles, const DevParams* Pd, const DevState& S);
 void lobk_finalize(hipStream_t st, bool t2, const DevParams* Pd, const DevState& S);
+
+// ---- lob_tu_stats.hip ----
+// What the episode-statistics reduction reads, as kernel arguments (the DevState does not grow and does not travel): the environment
+// field arrays of LOB_ENV_FIELDS it needs, the books' day words (null: no day groups) and the two session times of is_open
+#define LOB_STATS_BLOCK 256
+#define LOB_STATS_CHUNK 2048   // books per block: the unit that fixes the summation order (lob_kernels.h), so a constant
+struct StatsSrc {
+    const f64 *ep_reward, *ep_pnl, *ep_bandh;
+    const i32 *total_ticks, *market_buys, *market_sells, *done, *time_ms;
+    const i64 *ntr_snap, *tick_pos;
+    const i32* day;
+    i64 open_ms, close_ms;
+    u64 book_id_offset;
+    i32 B;
+};
+// out[0 .. n_groups): group 0 = every book, 1 + d = the books of day d; partial: n_groups * lobk_stats_chunks(B) records of scratch
+int lobk_stats_chunks(int B);
+void lobk_episode_stats(hipStream_t st, const StatsSrc& s, int n_groups, lob_episode_record* partial, lob_episode_record* out);
 
 // ---- lob_tu_learn.hip ----
 // learn_q_pair_kernel / learn_q_lane_kernel<algo, vt, tr>: vt = 8 when the state has eight variables (else 0)

@@ -56,6 +56,26 @@ def gen_stream_host(gen, depth, max_trades, first_book, n_books):
     return out
 
 
+# numpy view of abi.EpisodeStats (lob_episode_record): rows of Engine.episode_stats, operands of merge_episode_stats
+_STAT_F64 = np.dtype([("sum", "<f8"), ("sumsq", "<f8"), ("min", "<f8"), ("max", "<f8"), ("argmin", "<i8"), ("argmax", "<i8")])
+_STAT_I64 = np.dtype([("sum", "<i8"), ("sumsq", "<i8"), ("min", "<i8"), ("max", "<i8"), ("argmin", "<i8"), ("argmax", "<i8")])
+EPISODE_STATS_DTYPE = np.dtype([("group", "<i4"), ("n_books", "<i4"), ("n_live", "<i4"), ("n_terminal", "<i4"),
+                                ("n_out_of_data", "<i4"), ("n_rho", "<i4"), ("f", _STAT_F64, (4,)), ("i", _STAT_I64, (4,))])
+assert EPISODE_STATS_DTYPE.itemsize == C.sizeof(abi.EpisodeStats)
+
+
+def merge_episode_stats(a, b):
+    """lob_episode_stats_merge: the record of the books of `a` and `b` together (one row each, or arrays of equal length
+    merged row by row) -- how the records of several engines are put together.  Host only."""
+    lib = abi.load()
+    a, b = np.asarray(a, dtype=EPISODE_STATS_DTYPE), np.asarray(b, dtype=EPISODE_STATS_DTYPE)
+    assert a.shape == b.shape
+    o, f = np.array(a.reshape(-1), copy=True), np.ascontiguousarray(b.reshape(-1))
+    for k in range(o.shape[0]):
+        lib.lob_episode_stats_merge(_ptr(o[k:k + 1]), _ptr(f[k:k + 1]))
+    return o.reshape(a.shape)
+
+
 def _take_records(lib, ptr, n, depth, max_trades):
     W = lib.lob_record_words(depth, max_trades)
     buf = (C.c_uint32 * (n * W)).from_address(ptr.value)
@@ -197,6 +217,18 @@ class Engine:
         out = (abi.BookDump * n)()
         self._check(self.lib.lob_get_books(self.h, first, n, C.cast(out, C.c_void_p)))
         return out
+
+    def episode_stats(self, by_day=False):
+        """lob_episode_stats: the batch's episode statistics reduced on the device, one row (EPISODE_STATS_DTYPE) per record --
+        row 0 the whole engine, with by_day row 1 + d the books playing library day d."""
+        n = C.c_int32(0)
+        out = np.zeros(1, dtype=EPISODE_STATS_DTYPE)
+        rc = self.lib.lob_episode_stats(self.h, 1 if by_day else 0, _ptr(out), 1, C.byref(n))
+        if rc == abi.LOB_EINVAL and n.value > 1:   # one record per day as well: the call has said how many
+            out = np.zeros(n.value, dtype=EPISODE_STATS_DTYPE)
+            rc = self.lib.lob_episode_stats(self.h, 1, _ptr(out), out.shape[0], C.byref(n))
+        self._check(rc)
+        return out[:n.value]
 
     # ---- learner ----
     def td_step(self, n=1):

@@ -348,6 +348,21 @@ public:
         return os.str();
     }
     std::string getEpisodeId() { return "synthetic"; }
+    // The batch's episode statistics reduced on the device (lob_episode_stats): [0] every book; with by_day, [1 + d] the books
+    // playing library day d -- what getEpisodeReward / getMeanEpisodeReward / getEpisodePnL / getTotalTransactions say of one
+    // book (the test loop's Rwd, Rho, Pnl, nTr, Ppt, src/main.cpp:231-236), for all of them, without a dump per book
+    std::vector<lob_episode_record> EpisodeStats(bool by_day = false) {
+        std::vector<lob_episode_record> out(1);
+        int32_t n = 0;
+        int rc = lob_episode_stats(e_, by_day ? 1 : 0, out.data(), (int32_t)out.size(), &n);
+        if (rc == LOB_EINVAL && n > (int32_t)out.size()) {  // a record per day as well: the call has said how many
+            out.resize(n);
+            rc = lob_episode_stats(e_, 1, out.data(), (int32_t)out.size(), &n);
+        }
+        check(rc, "EpisodeStats");
+        out.resize(n);
+        return out;
+    }
 };
 
 // ---------------------------------------------------------------------------

@@ -5,6 +5,10 @@
 //
 //   lob_run -c config/engine.yaml [-n books] [-e episodes (default: training.n_episodes)] [-a sarsa|q_learn|double_q_learn|r_learn|online_r_learn|double_r_learn] [--events N] [--depth D]
 //           [--theta out.bin] [--profit-log profit_log.csv]
+//           [--batch-log FILE]   (or logging.batch_log: after every training episode and every greedy test round one CSV row for the
+//            WHOLE batch -- mean / std / min / max over the books of what the training_log row shows of book 0 -- and, with a
+//            directory of days, one more row per day that had books; reduced on the device, lob_episode_stats.  --gpus N: every
+//            rank writes FILE.rank<r>, its own shard)
 //           [--gpus N [--sync-every K]]   one process per GPU (forked here), -n books EACH, book ids rank * n ..,
 //            delta-theta all-reduced over RCCL/xGMI every K steps (include/lob_comm.h): the stand-in for the
 //            reference's N training threads on one shared Agent (src/main.cpp:196-206)
@@ -22,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <cmath>
 #include <random>
 
 #include "lob_host.hpp"
@@ -143,10 +148,45 @@ static DaySplit load_day_library(const lob::Config& c, const lob_params& p, cons
     return d;
 }
 
+// --batch-log: the episode statistics of the whole batch (lob_episode_stats), one row per group that has books.  `episode`: the
+// training episode's number, or "test<round>" for a greedy round over the held-out days; `epsilon`: the training row's column (the
+// policy's descr() after HandleTerminal).  std is the population figure from
+// sum and sum of squares, clamped at 0; rho's figures are over the books that made a step (n_rho); ppt = sum of pnl / sum of
+// transactions of the group (src/main.cpp:236 for one book).
+struct BatchLog {
+    FILE* f = nullptr;
+    ~BatchLog() { if (f) fclose(f); }
+    void open(const std::string& path) {
+        f = fopen(path.c_str(), "w");
+        if (!f) throw std::runtime_error("cannot write " + path);
+        fprintf(f, "episode,group,day_file,n_books,n_terminal,n_out_of_data,epsilon,reward_mean,reward_std,reward_min,reward_max,"
+                   "rho_mean,rho_std,rho_min,rho_max,pnl_mean,pnl_std,pnl_min,pnl_max,steps_mean,steps_min,steps_max,"
+                   "transactions_mean,transactions_min,transactions_max,ppt\n");
+    }
+    void write(const std::string& episode, lob::BatchedIntraday& env, const std::vector<std::array<std::string, 3>>* files, double epsilon) {
+        if (!f) return;
+        for (const lob_episode_record& r : env.EpisodeStats(files != nullptr)) {
+            if (r.group >= 0 && r.n_books == 0) continue;
+            fprintf(f, "%s,%d,%s,%d,%d,%d,%.6g", episode.c_str(), r.group, r.group >= 0 ? (*files)[r.group][1].c_str() : "", r.n_books, r.n_terminal,
+                    r.n_out_of_data, epsilon);
+            const int fq[3] = {LOB_STATF_REWARD, LOB_STATF_RHO, LOB_STATF_PNL};
+            for (int q : fq) {
+                const lob_stat_f64& s = r.f[q];
+                const double n = q == LOB_STATF_RHO ? r.n_rho : r.n_books, mean = s.sum / n, var = s.sumsq / n - mean * mean;
+                fprintf(f, ",%.10g,%.10g,%.10g,%.10g", mean, var > 0 ? std::sqrt(var) : 0.0, s.min, s.max);
+            }
+            const int iq[2] = {LOB_STATI_STEPS, LOB_STATI_TRANSACTIONS};
+            for (int q : iq) fprintf(f, ",%.10g,%lld,%lld", (double)r.i[q].sum / r.n_books, (long long)r.i[q].min, (long long)r.i[q].max);
+            fprintf(f, ",%.10g\n", r.f[LOB_STATF_PNL].sum / (double)r.i[LOB_STATI_TRANSACTIONS].sum);
+        }
+        fflush(f);
+    }
+};
+
 // The final testing phase (src/main.cpp:211-239): GoGreedy(), then every test day in a FRESH environment (main.cpp:214) with the
 // trained weights -- here one lock-step Backtester episode per n_books test days, book i of a round playing test day i
 // (LOB_DAYS_IN_ORDER) -- and the reference's five figures per day.  Private theta: every test book gets book 0's weights.
-static void evaluate_days(const lob::Config& c, const lob_params& p, const DaySplit& d, lob::BatchedIntraday& trained) {
+static void evaluate_days(const lob::Config& c, const lob_params& p, const DaySplit& d, lob::BatchedIntraday& trained, BatchLog& batch_log) {
     const int B = std::min(d.n_test, trained.n_books());
     lob_params q = p;
     q.book_id_offset = 0;
@@ -169,6 +209,7 @@ static void evaluate_days(const lob::Config& c, const lob_params& p, const DaySp
         env.SelectDays(LOB_DAYS_IN_ORDER, d.test_first + r0, n);
         lob::Backtester bt(env);
         if (!bt.RunEpisode(&agent)) { fprintf(stderr, "[!] no data in test days %d..%d\n", r0 + 1, r0 + n); continue; }
+        batch_log.write("test" + std::to_string(r0 / B + 1), env, &d.files, agent.epsilon_);
         for (int i = 0; i < n; i++) {
             const auto& f = d.files[d.test_first + r0 + i];
             const double pnl = env.getEpisodePnL(i);
@@ -180,7 +221,7 @@ static void evaluate_days(const lob::Config& c, const lob_params& p, const DaySp
 }
 
 static int run(int argc, char** argv, int rank, int world, const std::string& rdzv) {
-    std::string cfg_path, algo, theta_out, profit_log, stats_out, md, tas, lob_ob, lob_msg, md_dir, tas_dir;
+    std::string cfg_path, algo, theta_out, profit_log, stats_out, batch_log_path, md, tas, lob_ob, lob_msg, md_dir, tas_dir;
     int lob_levels = 0;
     int books = 1, episodes = -1, events = 2112, depth = 5, sync_every = 64;
     for (int i = 1; i < argc; i++) {
@@ -195,6 +236,7 @@ static int run(int argc, char** argv, int rank, int world, const std::string& rd
         else if (a == "--theta") theta_out = next();
         else if (a == "--profit-log") profit_log = next();
         else if (a == "--stats-out") stats_out = next();   // env.writeStats(output_dir + "test_stats.csv"), src/main.cpp:242
+        else if (a == "--batch-log") batch_log_path = next();
         else if (a == "--md") md = next();
         else if (a == "--tas") tas = next();
         else if (a == "--md-dir") md_dir = next();
@@ -243,6 +285,9 @@ static int run(int argc, char** argv, int rank, int world, const std::string& rd
         lob::Agent agent(env, c);
         lob::Learner learner(env, 8);
         if (comm) learner.set_comm(comm, sync_every);
+        BatchLog batch_log;
+        if (batch_log_path.empty()) batch_log_path = c.str("logging.batch_log", "");
+        if (!batch_log_path.empty()) batch_log.open(world > 1 ? batch_log_path + ".rank" + std::to_string(rank) : batch_log_path);
         if (rank == 0) printf("episode,episode_id,reward,pnl,n_steps,epsilon\n");
         for (int ep = 0; ep < episodes; ep++) {
             auto t0 = std::chrono::steady_clock::now();
@@ -254,11 +299,12 @@ static int run(int argc, char** argv, int rank, int world, const std::string& rd
             const std::string ep_id = days.n_train > 0 ? days.files[env.Days()[0]][1] : env.getEpisodeId();
             if (rank == 0) printf("%d,%s,%.10g,%.10g,%d,%.6g\n", ep + 1, ep_id.c_str(), env.getEpisodeReward(0), env.getEpisodePnL(0),
                    env.book(0).total_ticks, agent.epsilon_);
+            batch_log.write(std::to_string(ep + 1), env, days.n_train > 0 ? &days.files : nullptr, agent.epsilon_);
             fprintf(stderr, "[rank %d/%d] episode %d: %lld env-steps over %d books in %.3f s\n", rank, world, ep + 1, (long long)cnt[0], books, sec);
         }
         if (!theta_out.empty() && rank == 0) agent.write_theta(theta_out);  // replicas agree after the last exchange
         if (comm) { lob_comm_barrier(comm); lob_comm_destroy(comm); comm = nullptr; }
-        if (days.n_test > 0 && rank == 0) evaluate_days(c, p, days, env);
+        if (days.n_test > 0 && rank == 0) evaluate_days(c, p, days, env, batch_log);
         if (!profit_log.empty() && rank == 0) {
             // src/main.cpp:217-239: GoGreedy() then one Backtester episode with profit logging (book 0)
             agent.GoGreedy();
