@@ -434,6 +434,50 @@ int lob_handle_terminal(lob_engine* e);
  * the last read (at most `cap`; `n_lost`, if not NULL: rows that did not fit the device ring of 8192 or `cap`). */
 int lob_model_log_enable(lob_engine* e, int32_t on);
 int lob_model_log_read(lob_engine* e, double* rows, int32_t cap, int32_t* n_rows, int64_t* n_lost);
+
+/* ---- step log: the profit-log row of every step, recorded on the device -----
+ * Replaces Intraday::LogProfit (src/environment/intraday.cpp:438-451; schema src/experiment/serial.cpp:101-107), which the
+ * reference's Backtester calls after every step (src/environment/base.cpp:333) -- for any chosen set of books, inside the
+ * stream of steps: no dump, no copy and no synchronisation per step, and any number of steps per call.
+ *   Every field of a row is, bit for bit, what lob_get_books would report for that book had it been called right after that
+ * step.  The row carries the running totals: the step's own bandh / reward is the difference of two consecutive rows (row 0:
+ * from 0.0), taken by the caller in f64 -- the engine keeps the totals and nothing else.  sizeof == 96, a multiple of 16: the
+ * rows of the device log are 16-byte aligned (on the host the type has its natural alignment, 8).
+ *   What gets a row: every performAction that ran to its end (base.cpp:333), by lob_td_step, lob_eval_step, lob_td_step_begin +
+ * lob_td_step_end (written by the end half) and lob_step.  A step that runs out of data writes NONE (it returns at
+ * base.cpp:289-290 although it has counted its tick, base.cpp:278): such a book (terminal == 2) ends with total_ticks = its
+ * rows + 1, every other book with total_ticks = its rows, stored plus lost.  A book that is already over gets none, and
+ * lob_clear_inventory writes none.  The k-th logged step of a book (k from 0) is its row k; rows with k >= cap_steps are
+ * not stored but counted in n_lost -- the log never overwrites.
+ *   lob_step_log_enable: host_books = LOCAL book indices (as lob_get_books takes them), strictly ascending, within
+ * [0, n_books); NULL with n_sel == n_books selects every book.  n_sel == 0 switches the log off and frees its memory.  The log
+ * is sized n_sel x cap_steps x 96 B at this call (all 65 536 books of the headline batch: 6.3 MB per step, 8.8 GB for a
+ * 1 400-step episode): LOB_ENOMEM if that does not fit, LOB_EINVAL for a bad list or cap_steps < 1, LOB_ESTATE between
+ * lob_td_step_begin and lob_td_step_end.  Recording starts with the NEXT lob_reset and every lob_reset empties the log: it
+ * holds the current episode, never half of one.  While the log is on, a step issues one more kernel launch; off, none.
+ *   lob_step_log_counts: int32[n_sel] stored rows and (n_lost may be NULL) lost rows.  lob_step_log_read: book-major,
+ * host_out[(j - first_sel) * n_rows + (k - first_row)] = row k of selected book j; slots beyond a book's stored count are 96
+ * zero bytes (step == 0 marks "no row").  Both wait once for their own result and change no engine state.  LOB_ESTATE when
+ * the log is off or inside a half step, LOB_EINVAL for NULL or a range outside the selection or cap_steps. */
+typedef struct lob_step_row {
+    int64_t time_ms;                   /* dump.time_ms                     (market->time())            */
+    int64_t position;                  /* dump.position                    (risk_manager_.exposure())  */
+    double  midprice;                  /* (dump.ask_px[0] + dump.bid_px[0]) / 2.0, in f64              */
+    double  spread;                    /* dump.ask_px[0] - dump.bid_px[0], in f64                      */
+    double  ask_quote, bid_quote;      /* dump.ask_quote / bid_quote                                   */
+    double  pnl_step;                  /* dump.pnl_step                                                */
+    double  episode_pnl;               /* dump.episode_pnl     running totals: the step's own          */
+    double  episode_bandh;             /* dump.episode_bandh   bandh / reward is the difference of two */
+    double  episode_reward;            /* dump.episode_reward  consecutive rows (row 0: from 0.0)      */
+    int32_t step;                      /* dump.total_ticks after the step: >= 1 in every written row   */
+    int32_t action;                    /* dump.last_action                                             */
+    int32_t ask_level, bid_level;      /* dump.ask_level / bid_level                                   */
+} lob_step_row;
+int lob_step_log_enable(lob_engine* e, const int32_t* host_books, int32_t n_sel, int32_t cap_steps);
+int lob_step_log_counts(lob_engine* e, int32_t* n_rows, int32_t* n_lost);
+int lob_step_log_read(lob_engine* e, int32_t first_sel, int32_t n_sel, int32_t first_row, int32_t n_rows,
+                      lob_step_row* host_out);
+
 int lob_set_alpha(lob_engine* e, double alpha);
 int lob_set_epsilon(lob_engine* e, double epsilon);
 int lob_set_tau(lob_engine* e, double tau);

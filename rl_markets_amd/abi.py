@@ -125,6 +125,14 @@ class EpisodeStats(C.Structure):
                 ("n_out_of_data", C.c_int32), ("n_rho", C.c_int32), ("f", StatF64 * 4), ("i", StatI64 * 4)]
 
 
+class StepRow(C.Structure):
+    """lob_step_row: one profit-log row of the step log (lob_step_log_read), 96 bytes."""
+    _fields_ = [("time_ms", C.c_int64), ("position", C.c_int64), ("midprice", C.c_double), ("spread", C.c_double),
+                ("ask_quote", C.c_double), ("bid_quote", C.c_double), ("pnl_step", C.c_double), ("episode_pnl", C.c_double),
+                ("episode_bandh", C.c_double), ("episode_reward", C.c_double), ("step", C.c_int32), ("action", C.c_int32),
+                ("ask_level", C.c_int32), ("bid_level", C.c_int32)]
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LOB_ENGINE_LIB: an experiment build of the same library (tools/exp_prof.py, tools/exp_variants.sh)
 LIB_PATH = os.environ.get("LOB_ENGINE_LIB") or os.path.join(_HERE, "csrc", "liblob_engine.so")
@@ -187,6 +195,9 @@ def load():
         "lob_get_books": (C.c_int, [vp, C.c_int32, C.c_int32, vp]),
         "lob_episode_stats": (C.c_int, [vp, C.c_int32, vp, C.c_int32, P(C.c_int32)]),
         "lob_episode_stats_merge": (None, [vp, vp]),
+        "lob_step_log_enable": (C.c_int, [vp, vp, C.c_int32, C.c_int32]),
+        "lob_step_log_counts": (C.c_int, [vp, vp, vp]),
+        "lob_step_log_read": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]),
         "lob_td_step": (C.c_int, [vp, C.c_int32]),
         "lob_td_step_begin": (C.c_int, [vp]),
         "lob_td_split_supported": (C.c_int, [vp]),

@@ -1,7 +1,8 @@
 // Host side of the C ABI (include/lob_engine.h): device memory management,
 // kernel launches on one HIP stream, HIP-event kernel timing.  gfx950 only;
-// there is no CPU execution path in this file.  (One of the library's five translation units, lob_launch.h: the environment,
-// pre-pass, fast learner and episode-statistics kernels are compiled in lob_tu_env.hip / lob_tu_prepass.hip / lob_tu_learn.hip / lob_tu_stats.hip.)
+// there is no CPU execution path in this file.  (One of the library's six translation units, lob_launch.h: the environment,
+// pre-pass, fast learner, episode-statistics and step-log kernels are compiled in lob_tu_env.hip / lob_tu_prepass.hip / lob_tu_learn.hip /
+// lob_tu_stats.hip / lob_tu_steplog.hip.)
 #define LOB_TU_SPLIT 1
 #define LOB_TU_MAIN 1
 #include <hip/hip_runtime.h>
@@ -202,6 +203,14 @@ struct lob_engine {
     int dump_cap = 0;
     lob_episode_record* stats_dev = nullptr;   // lob_episode_stats: [stats_cap] result records, then the blocks' partial records
     size_t stats_cap = 0;
+    // lob_step_log_*: the device log of the selected books' profit-log rows (lob_tu_steplog.hip), all of it the engine's own
+    lob_step_row* slog_rows = nullptr;    // [slog_cap][slog_n], step-major
+    i32* slog_cnt = nullptr;              // [2][slog_n]: stored rows, lost rows
+    i32* slog_sel = nullptr;              // [slog_n] local book indices (null: every book)
+    int slog_n = 0, slog_cap = 0;         // slog_n == 0: the log is off
+    bool slog_armed = false;              // a lob_reset has come since lob_step_log_enable: the steps record
+    lob_step_row* slog_stage = nullptr;   // lob_step_log_read's book-major staging buffer, grown like dump_dev
+    size_t slog_stage_cap = 0;
     bool have_events = false, was_reset = false;
     bool episode_open = false;  // a pre-pass ran and its window sums have not been rolled back to the stop point yet
     bool model_log = false;     // lob_model_log_enable: the step sums |delta| (td_stats_kernel)
@@ -747,6 +756,14 @@ static void free_days(lob_engine* e) {
     e->lib_pending = false;
 }
 
+static void step_log_free(lob_engine* e) {
+    if (e->slog_rows) hipFree(e->slog_rows);
+    if (e->slog_cnt) hipFree(e->slog_cnt);
+    if (e->slog_sel) hipFree(e->slog_sel);
+    e->slog_rows = nullptr; e->slog_cnt = nullptr; e->slog_sel = nullptr;
+    e->slog_n = e->slog_cap = 0;
+    e->slog_armed = false;
+}
 void lob_destroy(lob_engine* e) {
     if (!e) return;
     hipSetDevice(e->device);
@@ -772,6 +789,8 @@ void lob_destroy(lob_engine* e) {
     if (e->track_dev) hipFree(e->track_dev);
     if (e->dump_dev) hipFree(e->dump_dev);
     if (e->stats_dev) hipFree(e->stats_dev);
+    step_log_free(e);
+    if (e->slog_stage) hipFree(e->slog_stage);
     if (e->spx_gather) hipFree(e->spx_gather);
     if (e->spx_ev) hipEventDestroy(e->spx_ev);
     if (e->spx_total_host) hipHostFree(e->spx_total_host);
@@ -1271,6 +1290,10 @@ int lob_reset(lob_engine* e) {
     HIPCHK(hipMemsetAsync(e->S.acc_list_n, 0, 2 * sizeof(i32), e->stream));
     HIPCHK(hipMemsetAsync(e->S.acc_pend, 0, (size_t)e->B, e->stream));
     if (e->S.dir_list_n) HIPCHK(hipMemsetAsync(e->S.dir_list_n, 0, 2 * sizeof(i32), e->stream));
+    if (e->slog_n) {   // the step log holds the episode that starts here (its rows need no clearing: the counts say which exist)
+        HIPCHK(hipMemsetAsync(e->slog_cnt, 0, 2 * (size_t)e->slog_n * sizeof(i32), e->stream));
+        e->slog_armed = true;
+    }
     if (e->half_open) {
         // a step abandoned between lob_td_step_begin and lob_td_step_end (a weight exchange that failed): its learner half never
         // ran, so the double-buffered lists are where the step found them -- the survivors of the combine table wait in the
@@ -1319,6 +1342,24 @@ static int not_mid_step(lob_engine* e, const char* who) {
     return LOB_OK;
 }
 
+// The step log's row of every selected book that has just completed a step (lob_tu_steplog.hip step_log_kernel): on the main stream
+// behind the step's last kernel; not launched while the log is off or waits for its first lob_reset.
+static void launch_step_log(lob_engine* e) {
+    if (!e->slog_armed) return;
+    TimedLaunch t(e, "step_log_kernel");
+    StepLogSrc s;
+    s.done = e->S.done; s.time_ms = e->S.time_ms; s.rec_cur = e->S.rec_cur; s.last_action = e->S.last_action;
+    s.ask_level = e->S.ask_level; s.bid_level = e->S.bid_level; s.total_ticks = e->S.total_ticks;
+    s.position = e->S.position;
+    s.ask_quote = e->S.ask_quote; s.bid_quote = e->S.bid_quote; s.pnl_step = e->S.pnl_step;
+    s.ep_pnl = e->S.ep_pnl; s.ep_bandh = e->S.ep_bandh; s.ep_reward = e->S.ep_reward;
+    s.records = e->S.records; s.rec_phase = e->S.rec_phase;
+    s.n_events = e->S.n_events; s.Wd = e->P.Wd; s.w_ask0 = drec_ask_px(e->P.D, e->P.T); s.w_bid0 = drec_bid_px(e->P.D, e->P.T);
+    s.sel = e->slog_sel; s.n_sel = e->slog_n; s.cap = e->slog_cap;
+    s.rows = e->slog_rows; s.n_rows = e->slog_cnt; s.n_lost = e->slog_cnt + e->slog_n;
+    lobk_step_log(e->stream, s);
+}
+
 int lob_step(lob_engine* e, const int32_t* host_actions) {
     int rc = need_reset(e, "lob_step");
     if (rc) return rc;
@@ -1335,6 +1376,7 @@ int lob_step(lob_engine* e, const int32_t* host_actions) {
         TimedLaunch t(e, "env_kernel");
         launch_env(e, e->stream, (const i32*)e->actions_dev, 0, 0, e->B, 0);
     }
+    launch_step_log(e);
     maybe_refill_track(e);
     HIPCHK(hipGetLastError());
     return check_device_errors(e);
@@ -1849,6 +1891,7 @@ static int run_steps(lob_engine* e, int32_t n_steps, int mode, int half = 0) {
         if (!sp.second) { e->half_open = true; continue; }
         e->half_open = false;
         { int rc = update_all(e, sp); if (rc) return rc; }
+        launch_step_log(e);
     }
     HIPCHK(hipGetLastError());
     return LOB_OK;
@@ -1913,6 +1956,83 @@ int lob_model_log_read(lob_engine* e, double* rows, int32_t cap, int32_t* n_rows
     HIPCHK(hipStreamSynchronize(e->stream));
     *n_rows = (int32_t)n;
     if (n_lost) *n_lost = cnt[1] - n;   // rows beyond the ring (LOB_ML_ROWS between two reads) or beyond `cap`
+    return LOB_OK;
+}
+
+// The step log (include/lob_engine.h): the log's memory belongs to the engine, not to DevState -- the step kernels never see it.
+int lob_step_log_enable(lob_engine* e, const int32_t* host_books, int32_t n_sel, int32_t cap_steps) {
+    if (!e) { lob_set_error("lob_step_log_enable: NULL engine"); return LOB_EINVAL; }
+    { int rc = not_mid_step(e, "lob_step_log_enable"); if (rc) return rc; }
+    HIPCHK(hipSetDevice(e->device));
+    if (n_sel == 0) {
+        HIPCHK(hipStreamSynchronize(e->stream));   // (steps still in flight write the log)
+        step_log_free(e);
+        return LOB_OK;
+    }
+    if (n_sel < 0 || n_sel > e->B || cap_steps < 1) { lob_set_error("lob_step_log_enable: n_sel outside [0, n_books] or cap_steps < 1"); return LOB_EINVAL; }
+    if (!host_books && n_sel != e->B) { lob_set_error("lob_step_log_enable: host_books == NULL selects every book: n_sel must be n_books"); return LOB_EINVAL; }
+    if (host_books)
+        for (int j = 0; j < n_sel; j++)
+            if (host_books[j] < 0 || host_books[j] >= e->B || (j > 0 && host_books[j] <= host_books[j - 1])) {
+                lob_set_error("lob_step_log_enable: the books must be strictly ascending and within [0, n_books)");
+                return LOB_EINVAL;
+            }
+    HIPCHK(hipStreamSynchronize(e->stream));
+    step_log_free(e);
+    hipError_t err = hipMalloc((void**)&e->slog_rows, (size_t)n_sel * (size_t)cap_steps * sizeof(lob_step_row));
+    if (err == hipSuccess) err = hipMalloc((void**)&e->slog_cnt, 2 * (size_t)n_sel * sizeof(i32));
+    if (err == hipSuccess && host_books) err = hipMalloc((void**)&e->slog_sel, (size_t)n_sel * sizeof(i32));
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        step_log_free(e);
+        lob_set_error(std::string("lob_step_log_enable: hipMalloc failed: ") + hipGetErrorString(err));
+        return LOB_ENOMEM;
+    }
+    e->slog_n = n_sel; e->slog_cap = cap_steps;
+    HIPCHK(hipMemsetAsync(e->slog_cnt, 0, 2 * (size_t)n_sel * sizeof(i32), e->stream));
+    if (host_books) HIPCHK(hipMemcpyAsync(e->slog_sel, host_books, (size_t)n_sel * sizeof(i32), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));   // (host_books is the caller's again)
+    return LOB_OK;
+}
+static int step_log_on(lob_engine* e, const char* who) {
+    if (!e) { lob_set_error(std::string(who) + ": NULL engine"); return LOB_EINVAL; }
+    if (!e->slog_n) { lob_set_error(std::string(who) + ": the step log is off (lob_step_log_enable)"); return LOB_ESTATE; }
+    return not_mid_step(e, who);
+}
+int lob_step_log_counts(lob_engine* e, int32_t* n_rows, int32_t* n_lost) {
+    int rc = step_log_on(e, "lob_step_log_counts");
+    if (rc) return rc;
+    if (!n_rows) { lob_set_error("lob_step_log_counts: n_rows == NULL"); return LOB_EINVAL; }
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipMemcpyAsync(n_rows, e->slog_cnt, (size_t)e->slog_n * sizeof(i32), hipMemcpyDeviceToHost, e->stream));
+    if (n_lost) HIPCHK(hipMemcpyAsync(n_lost, e->slog_cnt + e->slog_n, (size_t)e->slog_n * sizeof(i32), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return LOB_OK;
+}
+int lob_step_log_read(lob_engine* e, int32_t first_sel, int32_t n_sel, int32_t first_row, int32_t n_rows, lob_step_row* host_out) {
+    int rc = step_log_on(e, "lob_step_log_read");
+    if (rc) return rc;
+    if (!host_out || first_sel < 0 || n_sel < 1 || n_sel > e->slog_n - first_sel || first_row < 0 || n_rows < 1 || n_rows > e->slog_cap - first_row) {
+        lob_set_error("lob_step_log_read: NULL, or a range outside the selection or cap_steps");
+        return LOB_EINVAL;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    const size_t need = (size_t)n_sel * (size_t)n_rows;
+    if (e->slog_stage_cap < need) {
+        if (e->slog_stage) hipFree(e->slog_stage);
+        e->slog_stage = nullptr; e->slog_stage_cap = 0;
+        if (hipMalloc((void**)&e->slog_stage, need * sizeof(lob_step_row)) != hipSuccess) {
+            (void)hipGetLastError();
+            e->slog_stage = nullptr;
+            lob_set_error("lob_step_log_read: no room for the staging buffer (read fewer books or rows per call)");
+            return LOB_ENOMEM;
+        }
+        e->slog_stage_cap = need;
+    }
+    lobk_step_log_gather(e->stream, e->slog_rows, e->slog_cnt, e->slog_n, first_sel, n_sel, first_row, n_rows, e->slog_stage);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(host_out, e->slog_stage, need * sizeof(lob_step_row), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
     return LOB_OK;
 }
 

@@ -17,7 +17,7 @@
 #include "lob_launch.h"
 #include "lob_stats.h"
 
-// The engine library is built from five translation units (lob_launch.h).  The kernel TEMPLATES of these headers are only
+// The engine library is built from six translation units (lob_launch.h).  The kernel TEMPLATES of these headers are only
 // compiled where they are launched; the plain kernels are compiled in the unit that launches them: LOB_TU_SPLIT + one of
 // LOB_TU_MAIN / LOB_TU_ENV / LOB_TU_PREPASS / LOB_TU_LEARN / LOB_TU_STATS says which unit this is (neither: one unit holds everything, as the
 // experiment builds of tools/ and the host-side tests of the device headers do).

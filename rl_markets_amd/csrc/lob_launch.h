@@ -1,6 +1,6 @@
-// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is five
+// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is six
 // .hip files built in parallel: lob_engine.hip -- the C ABI's host side and the update / memo / trace kernels --, lob_tu_env.hip,
-// lob_tu_prepass.hip, lob_tu_learn.hip, lob_tu_stats.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
+// lob_tu_prepass.hip, lob_tu_learn.hip, lob_tu_stats.hip, lob_tu_steplog.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
 // lob_engine.hip used when it held the launches itself.  Kernels measured and lost (NOTES.md "Round 4") are only compiled with
 // -DLOB_EXPERIMENTS (tools/exp_variants.sh); a product build answers LOB_EXPERIMENTS-only requests with the product kernel.
 #ifndef LOB_LAUNCH_H
@@ -60,6 +60,28 @@ struct StatsSrc {
 // out[0 .. n_groups): group 0 = every book, 1 + d = the books of day d; partial: n_groups * lobk_stats_chunks(B) records of scratch
 int lobk_stats_chunks(int B);
 void lobk_episode_stats(hipStream_t st, const StatsSrc& s, int n_groups, lob_episode_record* partial, lob_episode_record* out);
+
+// ---- lob_tu_steplog.hip ----
+// What the step log reads and writes, as kernel arguments (the DevState does not grow and does not travel): the environment field
+// arrays of LOB_ENV_FIELDS behind a row of lob_step_row, the event records with the two words of a record that hold the touch
+// prices, the selection and the log itself.  rows[k * n_sel + j] = row k of selected book j (step-major: in the live phase the
+// lanes of a wave share k and write 64 x 96 B contiguous); n_rows / n_lost: [n_sel], one lane owns one book's two counters.
+struct StepLogSrc {
+    const i32 *done, *time_ms, *rec_cur, *last_action, *ask_level, *bid_level, *total_ticks;
+    const i64* position;
+    const f64 *ask_quote, *bid_quote, *pnl_step, *ep_pnl, *ep_bandh, *ep_reward;
+    const uint32_t* records;   // DevState::records / rec_phase (null: book b's stream starts at record b * n_events)
+    const i64* rec_phase;
+    i32 n_events, Wd, w_ask0, w_bid0;   // record stride in words; the words of a record holding ask_px[0] / bid_px[0]
+    const i32* sel;            // [n_sel] local book of selected j, ascending (null: j itself, every book)
+    i32 n_sel, cap;
+    lob_step_row* rows;
+    i32 *n_rows, *n_lost;
+};
+void lobk_step_log(hipStream_t st, const StepLogSrc& s);
+// out[(j - first_sel) * n_rows + (k - first_row)] = row k of selected book j, 96 zero bytes beyond the book's stored count
+void lobk_step_log_gather(hipStream_t st, const lob_step_row* rows, const i32* n_stored, int n_sel_all, int first_sel, int n_sel, int first_row,
+                          int n_rows, lob_step_row* out);
 
 // ---- lob_tu_learn.hip ----
 // learn_q_pair_kernel / learn_q_lane_kernel<algo, vt, tr>: vt = 8 when the state has eight variables (else 0)

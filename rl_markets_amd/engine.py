@@ -64,6 +64,13 @@ EPISODE_STATS_DTYPE = np.dtype([("group", "<i4"), ("n_books", "<i4"), ("n_live",
 assert EPISODE_STATS_DTYPE.itemsize == C.sizeof(abi.EpisodeStats)
 
 
+# numpy view of abi.StepRow (lob_step_row): the elements of Engine.step_log_read
+STEP_ROW_DTYPE = np.dtype([("time_ms", "<i8"), ("position", "<i8"), ("midprice", "<f8"), ("spread", "<f8"), ("ask_quote", "<f8"),
+                           ("bid_quote", "<f8"), ("pnl_step", "<f8"), ("episode_pnl", "<f8"), ("episode_bandh", "<f8"),
+                           ("episode_reward", "<f8"), ("step", "<i4"), ("action", "<i4"), ("ask_level", "<i4"), ("bid_level", "<i4")])
+assert STEP_ROW_DTYPE.itemsize == C.sizeof(abi.StepRow) == 96
+
+
 def merge_episode_stats(a, b):
     """lob_episode_stats_merge: the record of the books of `a` and `b` together (one row each, or arrays of equal length
     merged row by row) -- how the records of several engines are put together.  Host only."""
@@ -229,6 +236,39 @@ class Engine:
             rc = self.lib.lob_episode_stats(self.h, 1, _ptr(out), out.shape[0], C.byref(n))
         self._check(rc)
         return out[:n.value]
+
+    def step_log_enable(self, books, cap_steps):
+        """lob_step_log_enable: record the profit-log row of every completed step of `books` (local indices, strictly ascending;
+        None: every book) on the device, up to cap_steps rows per book, from the next reset() on.  books == []: off."""
+        if books is None:
+            n, rc = self.B, self.lib.lob_step_log_enable(self.h, None, self.B, cap_steps)
+        else:
+            sel = np.ascontiguousarray(books, dtype=np.int32).reshape(-1)
+            n, rc = int(sel.shape[0]), self.lib.lob_step_log_enable(self.h, _ptr(sel) if sel.shape[0] else None, sel.shape[0], cap_steps)
+        if rc == abi.LOB_OK:
+            self._slog_n, self._slog_cap = n, cap_steps
+        elif rc == abi.LOB_ENOMEM:     # (a refused list or state leaves the log as it was; this has switched it off)
+            self._slog_n = 0
+        self._check(rc)
+
+    def step_log_counts(self):
+        """lob_step_log_counts: (stored rows, lost rows) of every selected book, int32[n_sel] each."""
+        n = getattr(self, "_slog_n", 0)
+        rows, lost = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+        self._check(self.lib.lob_step_log_counts(self.h, _ptr(rows), _ptr(lost)))
+        return rows[:n], lost[:n]
+
+    def step_log_read(self, first_sel=0, n_sel=None, first_row=0, n_rows=None):
+        """lob_step_log_read: ndarray[n_sel, n_rows] of STEP_ROW_DTYPE, element [j, k] = row first_row + k of selected book
+        first_sel + j; slots beyond a book's stored count are zero (step == 0).  Defaults: the rest of the selection, and rows
+        up to the longest stored count (at least one)."""
+        if n_sel is None:
+            n_sel = getattr(self, "_slog_n", 0) - first_sel
+        if n_rows is None:
+            n_rows = max(1, int(self.step_log_counts()[0].max(initial=0)) - first_row)
+        out = np.zeros((max(n_sel, 1), max(n_rows, 1)), dtype=STEP_ROW_DTYPE)
+        self._check(self.lib.lob_step_log_read(self.h, first_sel, n_sel, first_row, n_rows, _ptr(out)))
+        return out[:max(n_sel, 0), :max(n_rows, 0)]
 
     # ---- learner ----
     def td_step(self, n=1):

@@ -27,6 +27,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -541,48 +542,86 @@ public:
 };
 
 class Backtester : public Runner {
-    std::ofstream profit_log_;
-    double last_bandh_ = 0.0;
+    std::vector<std::ofstream> profit_logs_;   // one per logged book
+    std::vector<int32_t> log_books_;
+    int steps_per_call_;
     int date_ = 0;
 
 protected:
     bool _step(Agent*) override {
-        check(lob_eval_step(environment.handle(), 1), "Backtester::_step");
+        check(lob_eval_step(environment.handle(), steps_per_call_), "Backtester::_step");
         environment.invalidate();
-        if (profit_log_.is_open()) LogProfit();
         return n_live() == 0;
     }
-    // Intraday::LogProfit (src/environment/intraday.cpp:438-451), book 0, one row per performed step
-    void LogProfit() {
-        int32_t stepped = 0;
-        {
-            std::vector<int32_t> st(environment.n_books());
-            check(lob_get_stepped(environment.handle(), st.data()), "LogProfit");
-            stepped = st[0];
+    // Intraday::LogProfit (src/environment/intraday.cpp:438-451), one line per performed step: the rows the device recorded during
+    // the episode (lob_step_log_*), handed over in bulk; bandh_step is the f64 difference of consecutive episode_bandh
+    void FlushProfit() {
+        const int32_t n = (int32_t)log_books_.size();
+        std::vector<int32_t> n_rows(n), n_lost(n);
+        check(lob_step_log_counts(environment.handle(), n_rows.data(), n_lost.data()), "LogProfit");
+        const int32_t chunk = 4096;
+        std::vector<lob_step_row> rows;
+        for (int32_t j = 0; j < n; j++) {
+            if (n_lost[j] > 0)
+                throw std::runtime_error("profit log of book " + std::to_string(log_books_[j]) + ": " + std::to_string(n_lost[j]) +
+                                         " steps beyond the log's capacity (start_logging's cap_steps)");
+            double last_bandh = 0.0;
+            for (int32_t k0 = 0; k0 < n_rows[j]; k0 += chunk) {
+                const int32_t m = std::min(chunk, n_rows[j] - k0);
+                rows.resize(m);
+                check(lob_step_log_read(environment.handle(), j, 1, k0, m, rows.data()), "LogProfit");
+                for (const lob_step_row& d : rows) {
+                    char buf[512];
+                    snprintf(buf, sizeof buf, "%d,%lld,%d,%lld,%.10g,%.10g,%.10g,%.10g,%d,%d,%.10g,%.10g\n", date_, (long long)d.time_ms,
+                             d.action, (long long)d.position, d.midprice, d.spread, d.ask_quote,
+                             d.bid_quote, d.ask_level, d.bid_level, d.pnl_step, d.episode_bandh - last_bandh);
+                    profit_logs_[j] << buf;
+                    last_bandh = d.episode_bandh;
+                }
+            }
+            profit_logs_[j].flush();
         }
-        if (!stepped) return;
-        lob_book_dump d = environment.book(0);
-        char buf[512];
-        snprintf(buf, sizeof buf, "%d,%lld,%d,%lld,%.10g,%.10g,%.10g,%.10g,%d,%d,%.10g,%.10g\n", date_, (long long)d.time_ms,
-                 d.last_action, (long long)d.position, (d.ask_px[0] + d.bid_px[0]) / 2.0, d.ask_px[0] - d.bid_px[0], d.ask_quote,
-                 d.bid_quote, d.ask_level, d.bid_level, d.pnl_step, d.episode_bandh - last_bandh_);
-        profit_log_ << buf;
-        last_bandh_ = d.episode_bandh;
     }
 
 public:
-    explicit Backtester(BatchedIntraday& env) : Runner(env) {}
-    // Backtester ctor + Base::start_logging (serial.cpp:97-122): profit_log.csv with the reference's header
-    void start_logging(const std::string& path, int date = 0) {
-        profit_log_.open(path.c_str());
-        if (!profit_log_.is_open()) throw std::runtime_error("Loggers not registered!");  // base.cpp:402-403
-        profit_log_ << "episode,step,action,position,midprice,spread,quoted_ask,quoted_bid,ask_level,bid_level,pnl_step,bandh_step\n";
-        date_ = date;
+    // steps_per_call: how many env-steps of every book are enqueued per host round trip
+    explicit Backtester(BatchedIntraday& env, int steps_per_call = 1) : Runner(env), steps_per_call_(steps_per_call < 1 ? 1 : steps_per_call) {}
+    ~Backtester() { if (!log_books_.empty()) lob_step_log_enable(environment.handle(), nullptr, 0, 0); }
+    // Backtester ctor + Base::start_logging (serial.cpp:97-122): profit_log.csv with the reference's header, book 0.  The rows are
+    // recorded on the device from the next RunEpisode on, at most cap_steps per episode (96 B each)
+    void start_logging(const std::string& path, int date = 0, int cap_steps = 1 << 16) {
+        start_logging_list(std::vector<std::string>{path}, std::vector<int32_t>{0}, date, cap_steps);
     }
-    void stop_logging() { profit_log_.close(); }
+    // ... of `count` books from `first` on, book b into "<path>.<b>"
+    void start_logging_books(const std::string& path, int first, int count, int date = 0, int cap_steps = 1 << 16) {
+        std::vector<std::string> paths;
+        std::vector<int32_t> books;
+        for (int b = first; b < first + count; b++) { paths.push_back(path + "." + std::to_string(b)); books.push_back(b); }
+        start_logging_list(paths, books, date, cap_steps);
+    }
+    void start_logging_list(const std::vector<std::string>& paths, const std::vector<int32_t>& books, int date, int cap_steps) {
+        stop_logging();
+        if (paths.empty() || paths.size() != books.size()) throw std::invalid_argument("start_logging: one path per book");
+        for (const std::string& path : paths) {
+            profit_logs_.emplace_back(path.c_str());
+            if (!profit_logs_.back().is_open()) { profit_logs_.clear(); throw std::runtime_error("Loggers not registered!"); }  // base.cpp:402-403
+            profit_logs_.back() << "episode,step,action,position,midprice,spread,quoted_ask,quoted_bid,ask_level,bid_level,pnl_step,bandh_step\n";
+        }
+        date_ = date;
+        const int rc = lob_step_log_enable(environment.handle(), books.data(), (int32_t)books.size(), cap_steps);
+        if (rc != LOB_OK) profit_logs_.clear();
+        check(rc, "start_logging");
+        log_books_ = books;
+    }
+    void stop_logging() {
+        if (!log_books_.empty()) check(lob_step_log_enable(environment.handle(), nullptr, 0, 0), "stop_logging");
+        log_books_.clear();
+        profit_logs_.clear();
+    }
     bool RunEpisode(Agent* m) override {
-        last_bandh_ = 0.0;
-        return Runner::RunEpisode(m);
+        if (!Runner::RunEpisode(m)) return false;
+        if (!log_books_.empty()) FlushProfit();
+        return true;
     }
 };
 

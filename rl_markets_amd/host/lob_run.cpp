@@ -4,7 +4,8 @@
 // rows of the reference's training_log (serial.cpp:81-88) for book 0.
 //
 //   lob_run -c config/engine.yaml [-n books] [-e episodes (default: training.n_episodes)] [-a sarsa|q_learn|double_q_learn|r_learn|online_r_learn|double_r_learn] [--events N] [--depth D]
-//           [--theta out.bin] [--profit-log profit_log.csv]
+//           [--theta out.bin] [--profit-log profit_log.csv [--profit-log-books first:count]]   (the greedy backtest's profit log of book 0;
+//            with --profit-log-books one file profit_log.csv.<book> per book of the range; recorded on the device, lob_step_log_*)
 //           [--batch-log FILE]   (or logging.batch_log: after every training episode and every greedy test round one CSV row for the
 //            WHOLE batch -- mean / std / min / max over the books of what the training_log row shows of book 0 -- and, with a
 //            directory of days, one more row per day that had books; reduced on the device, lob_episode_stats.  --gpus N: every
@@ -222,7 +223,7 @@ static void evaluate_days(const lob::Config& c, const lob_params& p, const DaySp
 
 static int run(int argc, char** argv, int rank, int world, const std::string& rdzv) {
     std::string cfg_path, algo, theta_out, profit_log, stats_out, batch_log_path, md, tas, lob_ob, lob_msg, md_dir, tas_dir;
-    int lob_levels = 0;
+    int lob_levels = 0, plog_first = 0, plog_count = 0;
     int books = 1, episodes = -1, events = 2112, depth = 5, sync_every = 64;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -235,6 +236,10 @@ static int run(int argc, char** argv, int rank, int world, const std::string& rd
         else if (a == "--depth") depth = atoi(next().c_str());
         else if (a == "--theta") theta_out = next();
         else if (a == "--profit-log") profit_log = next();
+        else if (a == "--profit-log-books") {
+            const std::string v = next();
+            if (sscanf(v.c_str(), "%d:%d", &plog_first, &plog_count) != 2 || plog_first < 0 || plog_count < 1) { fprintf(stderr, "--profit-log-books first:count\n"); return 1; }
+        }
         else if (a == "--stats-out") stats_out = next();   // env.writeStats(output_dir + "test_stats.csv"), src/main.cpp:242
         else if (a == "--batch-log") batch_log_path = next();
         else if (a == "--md") md = next();
@@ -308,8 +313,9 @@ static int run(int argc, char** argv, int rank, int world, const std::string& rd
         if (!profit_log.empty() && rank == 0) {
             // src/main.cpp:217-239: GoGreedy() then one Backtester episode with profit logging (book 0)
             agent.GoGreedy();
-            lob::Backtester bt(env);
-            bt.start_logging(profit_log, 20200102);
+            lob::Backtester bt(env, 8);
+            if (plog_count > 0) bt.start_logging_books(profit_log, plog_first, plog_count, 20200102);
+            else bt.start_logging(profit_log, 20200102);
             if (!bt.RunEpisode(&agent)) { fprintf(stderr, "[!] no data\n"); return 2; }
             bt.stop_logging();
             printf("backtest,%.10g,%.10g,%d\n", env.getEpisodeReward(0), env.getEpisodePnL(0), env.book(0).total_ticks);
