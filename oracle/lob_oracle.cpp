@@ -1006,6 +1006,9 @@ struct oracle_learner {
     std::vector<double> rho;  // RLearn / OnlineRLearn::rho (include/rl/agent.h:131,145): one per agent (1 shared, B private)
     double& rh(int b) { return rho[P.theta_mode == LOB_THETA_PRIVATE ? b : 0]; }
     int64_t n_steps_done = 0, n_updates = 0;
+    // oracle_set_days: the day each book plays from the next oracle_reset on (the caller's buffer)
+    std::vector<const uint32_t*> next_rec;
+    std::vector<int> next_len;
 
     double* th(int b) { return theta[P.theta_mode == LOB_THETA_PRIVATE ? b : 0].data(); }
     double* thb(int b) { return theta_b[P.theta_mode == LOB_THETA_PRIVATE ? b : 0].data(); }
@@ -1193,12 +1196,28 @@ oracle_learner* oracle_create(const lob_params* p, int32_t n_books, const uint32
     return o;
 }
 void oracle_destroy(oracle_learner* o) { delete o; }
+int oracle_set_days(oracle_learner* o, const uint32_t* records, const int64_t* first, const int32_t* len) {
+    const int W = lob_rec_words(o->P.depth, o->P.max_trades);
+    for (int b = 0; b < o->B; b++)
+        if (first[b] < 0 || len[b] < 2) return -1;  // (lob_load_days refuses a day of one event)
+    o->next_rec.resize(o->B);
+    o->next_len.resize(o->B);
+    for (int b = 0; b < o->B; b++) { o->next_rec[b] = records + (size_t)first[b] * W; o->next_len[b] = len[b]; }
+    return 0;
+}
 void oracle_debug_pass_stats(long long* out16, int reset) {
     for (int i = 0; i < 16; i++) { out16[i] = g_pass_stats[i]; if (reset) g_pass_stats[i] = 0; }
 }
 
 int oracle_reset(oracle_learner* o) {
     o->have_from = false;  // a step abandoned after its first half (no oracle_td_step_end) ends with its episode: lob_reset does the same
+    if (!o->next_rec.empty()) {
+        // the day set chosen since the last reset (src/main.cpp:53-55: rs.sample() + LoadData before RunEpisode); nothing of
+        // the learner moves, and Initialise below runs over the window sums the last episode left behind (quirk Q7)
+        for (int b = 0; b < o->B; b++) { o->env[b]->rec = o->next_rec[b]; o->env[b]->n_events = o->next_len[b]; }
+        o->next_rec.clear();
+        o->next_len.clear();
+    }
     for (int b = 0; b < o->B; b++) {
         bool ok = o->env[b]->Initialise();
         o->done[b] = ok ? 0 : 2;

@@ -48,6 +48,12 @@ typedef struct oracle_learner oracle_learner;
 oracle_learner* oracle_create(const lob_params* p, int32_t n_books, const uint32_t* records,
                               int32_t n_events);
 void oracle_destroy(oracle_learner* o);
+/* A day per book (the day library, lob_load_days / lob_days_set / lob_days_select): from the NEXT oracle_reset on -- the moment
+ * lob_reset swaps the engine's day sets -- book b plays records[first[b] .. first[b] + len[b]) (first in records of W words,
+ * `records` a flat buffer the caller keeps alive).  Nothing of the learner is touched: theta, traces, RNG counters, epsilon,
+ * rho and the window sums that persist across episodes stay as they are (src/main.cpp:53-55: rs.sample() + LoadData in
+ * front of RunEpisode).  Returns -1 for a negative offset or a day of fewer than 2 events. */
+int oracle_set_days(oracle_learner* o, const uint32_t* records, const int64_t* first, const int32_t* len);
 int oracle_reset(oracle_learner* o);                       /* Runner::RunEpisode prologue */
 int oracle_td_step(oracle_learner* o, int32_t n_steps);    /* n x Learner::_step */
 /* the rows Agent::HandleTransition hands to its "model_log" logger (src/rl/agent.cpp:93-100), all of them so far; returns their number */

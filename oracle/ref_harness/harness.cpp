@@ -20,7 +20,9 @@
 //   episode  : replay one book of a binary event stream (lob_engine.h record
 //              layout, depth 5) through Intraday + agent, mirroring
 //              Learner::_step (src/experiment/serial.cpp:53-70); writes a
-//              trajectory file.
+//              trajectory file.  --stream / --events (and --steps) may be comma-separated
+//              lists: episode k then loads entry k, a different day per episode --
+//              the rs.sample() + LoadData of src/main.cpp:53-55.
 //   learner  : same inputs through the reference's own Learner::RunEpisode
 //              (src/experiment/serial.cpp:72-93); prints steps and seconds
 //              (CPU baseline) and optionally dumps theta.
@@ -230,6 +232,19 @@ static Args parse(int argc, char** argv, int from) {
     return a;
 }
 
+// entry k of a comma-separated list (the last one when the list is shorter)
+static std::string list_entry(const std::string& s, int k) {
+    size_t from = 0;
+    for (int i = 0; i < k; i++) {
+        size_t c = s.find(',', from);
+        if (c == std::string::npos) break;
+        from = c + 1;
+    }
+    size_t to = s.find(',', from);
+    return s.substr(from, to == std::string::npos ? std::string::npos : to - from);
+}
+static int list_size(const std::string& s) { return 1 + (int)std::count(s.begin(), s.end(), ','); }
+
 static std::unique_ptr<rl::Policy> make_policy(const Args& a) {
     if (a.get("policy", "epsilon_greedy") == "boltzmann") return std::unique_ptr<rl::Policy>(new ReplayBoltzmann(9, a.getd("tau", 1.0)));
     return std::unique_ptr<rl::Policy>(new ReplayPolicy(9, a.getd("eps", 0.8)));
@@ -341,7 +356,7 @@ template <class A> static void dump_theta_b(A& ag, const std::string& path) {
 
 template <class AGENT>
 static int run_episode(const Args& a, Config& c, ProbeEnv& env, const std::string& out_path) {
-    long max_steps = a.geti("steps", 1L << 40);
+    const std::string steps_list = a.get("steps", std::to_string(1L << 40));   // one cap, or one per episode
     ProbeAgent<AGENT> agent(make_policy(a), c);
     if (a.kv.count("theta_in")) {
         FILE* f = fopen(a.get("theta_in").c_str(), "rb");
@@ -373,8 +388,9 @@ static int run_episode(const Args& a, Config& c, ProbeEnv& env, const std::strin
     std::string ends;
     const int episodes = (int)a.geti("episodes", 1);
     for (int ep = 0; ep < episodes; ep++) {
-        // src/main.cpp:55: every episode re-opens its data files
-        if (ep > 0) env.LoadData(a.get("ticker", "HSBA.L"), a.get("md"), a.get("tas"));
+        // src/main.cpp:53-55: every episode opens the data files of its day (the same ones again when one stream was given)
+        if (ep > 0) env.LoadData(a.get("ticker", "HSBA.L"), list_entry(a.get("md"), ep), list_entry(a.get("tas"), ep));
+        const long max_steps = atol(list_entry(steps_list, ep).c_str());
         // Runner::RunEpisode prologue (src/experiment/serial.cpp:18-26)
         if (!env.Initialise()) { fprintf(stderr, "Initialise failed\n"); return 3; }
         last_state->newState(env);
@@ -677,7 +693,23 @@ int main(int argc, char** argv) {
     long book = a.geti("book", 0);
     std::string tmp = a.get("tmp", "/tmp/ref_harness_" + std::to_string((long)getpid()));
     std::string md = tmp + "_md.csv", tas = tmp + "_tas.csv", yaml = tmp + ".yaml";
-    if (a.kv.count("stream")) {
+    const bool per_episode = mode == "episode" && a.kv.count("stream") && list_size(a.get("stream")) > 1;
+    if (per_episode) {
+        // a stream per episode: its own pair of CSVs each, handed over as lists
+        const int n = list_size(a.get("stream"));
+        if (list_size(a.get("events")) != n) { fprintf(stderr, "--stream and --events: lists of different length\n"); return 2; }
+        std::string mds, tass;
+        for (int k = 0; k < n; k++) {
+            const int ne = atoi(list_entry(a.get("events"), k).c_str());
+            const std::string mk = tmp + "_" + std::to_string(k) + "_md.csv", tk = tmp + "_" + std::to_string(k) + "_tas.csv";
+            auto rec = load_book(list_entry(a.get("stream"), k), D, T, ne, book);
+            write_csvs(rec, D, T, ne, mk, tk);
+            mds += (k ? "," : "") + mk;
+            tass += (k ? "," : "") + tk;
+        }
+        md = mds;
+        tas = tass;
+    } else if (a.kv.count("stream")) {
         auto rec = load_book(a.get("stream"), D, T, n_events, book);
         write_csvs(rec, D, T, n_events, md, tas);
     } else {
@@ -715,7 +747,7 @@ int main(int argc, char** argv) {
     }
 #endif
     ProbeEnv env(c);
-    env.LoadData(a.get("ticker", "HSBA.L"), md, tas);
+    env.LoadData(a.get("ticker", "HSBA.L"), list_entry(md, 0), list_entry(tas, 0));
     std::string algo = a.get("algo", "sarsa");
     int rc;
     if (mode == "episode") {
@@ -739,8 +771,10 @@ int main(int argc, char** argv) {
         rc = 1;
     }
     if (!a.geti("keep", 0) && a.kv.count("stream")) {
-        remove(md.c_str());
-        remove(tas.c_str());
+        for (int k = 0; k < list_size(md); k++) {
+            remove(list_entry(md, k).c_str());
+            remove(list_entry(tas, k).c_str());
+        }
     }
     remove(yaml.c_str());
     return rc;

@@ -57,6 +57,8 @@ def load():
     lib.oracle_create.restype = vp
     lib.oracle_create.argtypes = [P(abi.Params), C.c_int32, vp, C.c_int32]
     lib.oracle_destroy.argtypes = [vp]
+    lib.oracle_set_days.restype = C.c_int
+    lib.oracle_set_days.argtypes = [vp, vp, vp, vp]
     for n in ("oracle_reset", "oracle_clear_inventory", "oracle_handle_terminal", "oracle_td_step_begin", "oracle_td_step_end"):
         getattr(lib, n).argtypes = [vp]
     lib.oracle_td_step.argtypes = [vp, C.c_int32]
@@ -114,6 +116,19 @@ class Oracle:
 
     def __del__(self):
         self.close()
+
+    def set_days(self, library_records, first, length):
+        """From the next reset() on, book b plays library_records[first[b] : first[b] + length[b]] (oracle_set_days): a flat
+        [n_records][W] uint32 buffer, kept alive here.  The learner's state is not touched."""
+        lib_rec = np.ascontiguousarray(library_records, dtype=np.uint32)
+        first = np.ascontiguousarray(first, dtype=np.int64)
+        length = np.ascontiguousarray(length, dtype=np.int32)
+        assert lib_rec.ndim == 2 and lib_rec.shape[1] == self.records.shape[2], (lib_rec.shape, self.records.shape)
+        assert first.shape == (self.B,) and length.shape == (self.B,)
+        assert (first >= 0).all() and (first + length <= lib_rec.shape[0]).all()
+        assert self.lib.oracle_set_days(self.h, ptr(lib_rec), ptr(first), ptr(length)) == 0, "oracle_set_days"
+        # (the day being played is read until the next reset: the buffer before this one stays alive as well)
+        self._day_bufs = (getattr(self, "_day_bufs", ()) + (lib_rec,))[-2:]
 
     def reset(self):
         self.lib.oracle_reset(self.h)
@@ -176,6 +191,22 @@ class Oracle:
         return c
 
 
+class DayLibrary:
+    """The engine's view of a day library for Oracle.set_days: the days back to back in one buffer (what Engine.load_days
+    hands to lob_load_days) and their day_first / day_len tables."""
+
+    def __init__(self, days):
+        self.records = np.ascontiguousarray(np.concatenate([np.asarray(d, dtype=np.uint32) for d in days]))
+        self.day_len = np.array([len(d) for d in days], dtype=np.int32)
+        self.day_first = np.concatenate([[0], np.cumsum(self.day_len[:-1], dtype=np.int64)]).astype(np.int64)
+
+    def of(self, day_of_book):
+        """(library_records, first, length) for the books' days, e.g. DayLibrary(days).of(eng.days())."""
+        d = np.asarray(day_of_book, dtype=np.int64)
+        assert d.min() >= 0 and d.max() < len(self.day_len)
+        return self.records, self.day_first[d], self.day_len[d]
+
+
 def have_ref():
     return os.path.exists(REF_HARNESS) and os.access(REF_HARNESS, os.X_OK)
 
@@ -185,14 +216,15 @@ def run_ref_episode(records_book, depth=5, trades=2, algo="sarsa", mem=1 << 20, 
     """Run one book through the UNMODIFIED reference (oracle/_ref/ref_harness).
     Returns (trajectory ndarray of STEP_DTYPE, info dict, sparse theta (idx, val))."""
     assert have_ref(), "oracle/_ref/ref_harness not built (make -C oracle ref)"
-    rec = np.ascontiguousarray(records_book, dtype=np.uint32)
-    n_events = rec.shape[0]
+    # one stream, or a list of them: a day per episode (the harness's comma-separated --stream / --events)
+    recs = [np.ascontiguousarray(r, dtype=np.uint32) for r in (records_book if isinstance(records_book, (list, tuple)) else [records_book])]
     with tempfile.TemporaryDirectory() as td:
-        sp = os.path.join(td, "s.bin")
-        rec.tofile(sp)
+        sps = [os.path.join(td, "s%d.bin" % k) for k in range(len(recs))]
+        for r, sp in zip(recs, sps):
+            r.tofile(sp)
         out = os.path.join(td, "t.traj")
         th = os.path.join(td, "theta.bin")
-        cmd = [REF_HARNESS, "episode", "--stream", sp, "--events", str(n_events), "--book", "0",
+        cmd = [REF_HARNESS, "episode", "--stream", ",".join(sps), "--events", ",".join(str(r.shape[0]) for r in recs), "--book", "0",
                "--depth", str(depth), "--trades", str(trades), "--algo", algo, "--mem", str(mem),
                "--seed", str(seed), "--rng_stream", str(rng_stream), "--eps", repr(eps), "--out", out,
                "--tmp", os.path.join(td, "h")]

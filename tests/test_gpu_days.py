@@ -1,11 +1,12 @@
 """The day library (lob_load_days): recorded days resident in HBM, a day drawn per book and episode on the device
 (days_draw_kernel), the reference's training loop (src/main.cpp:51-55) and test loop (src/main.cpp:215-239).
 
-Against the oracle a book of the library is a one-book oracle over its own day.  The oracle cannot change days between
-episodes, but it reads its records in place: the second episode's day is written over the first in the oracle's buffer,
-so a book switches between two days of the SAME length (the library holds its lengths in pairs).  A day padded to a
-longer length with time-and-sales-dry rows is not the same day to the oracle (tests/test_days_abi.py shows where they part),
-so there is no batched oracle over unequal days here: every test of unequal days uses private theta."""
+Against the oracle a book of the library is a one-book oracle over its own day.  The oracle reads its records in place, so a
+book can switch between two days of the SAME length by writing the second over the first in the oracle's buffer (the library
+holds its lengths in pairs), and it changes to a day of ANOTHER length through Oracle.set_days (oracle_set_days, pinned by
+tests/test_oracle_days.py) -- a day padded to a longer length with time-and-sales-dry rows is not the same day to the oracle
+(tests/test_days_abi.py shows where they part).  The tests here use private theta; one weight vector over unequal days is
+tests/test_gpu_days_shared.py, against the batched oracle over days."""
 import numpy as np
 import pytest
 
@@ -59,7 +60,8 @@ def compare_book(ev, b, orc, tag):
 
 def test_explicit_days_match_oracle():
     """B = 24, private theta, 6 days of 300-900 events in three pairs of equal length; two episodes with different
-    lob_days_set assignments, every step against one-book oracles."""
+    lob_days_set assignments (the other day of the pair, written over the first in the oracle's buffer), then a third whose
+    assignment changes the length of every book's day (Oracle.set_days); every step against one-book oracles."""
     B, steps = 24, 200
     lengths = [310, 310, 620, 620, 900, 900]
     days = make_days(lengths)
@@ -67,6 +69,9 @@ def test_explicit_days_match_oracle():
     ep1 = rng.integers(0, 6, size=B).astype(np.int32)
     ep1[:6] = np.arange(6)
     ep2 = (ep1 ^ 1).astype(np.int32)   # the other day of the pair: same length, other content
+    ep3 = ((ep2 + 2) % 6).astype(np.int32)   # the next pair: another length for every book
+    assert (np.array(lengths)[ep3] != np.array(lengths)[ep2]).all()
+    lib = ol.DayLibrary(days)
     p = params()
     eng = engine.Engine(p, B)
     eng.load_days(days)
@@ -74,11 +79,14 @@ def test_explicit_days_match_oracle():
     for b in range(B):
         p1 = params(first_book=b)
         orcs.append(ol.Oracle(p1, days[ep1[b]][None].copy()))
-    for ep, assign in enumerate((ep1, ep2)):
+    for ep, assign in enumerate((ep1, ep2, ep3)):
         eng.days_set(assign)
-        if ep:
+        if ep == 1:
             for b in range(B):
                 orcs[b].records[0][...] = days[assign[b]]   # (in place: the oracle reads this buffer)
+        elif ep == 2:
+            for b in range(B):
+                orcs[b].set_days(*lib.of(assign[b:b + 1]))
         eng.reset()
         np.testing.assert_array_equal(eng.days(), assign)
         for o in orcs:
@@ -175,12 +183,10 @@ def test_in_order_days():
 def test_library_at_scale_ring_mode(monkeypatch, algo):
     """16 384 books, private theta, 8 days in four pairs of unequal length, the longest longer than the track ring
     (LOB_TRACK_RING = 1024: ring mode for every book); three episodes with a fresh random draw each, every episode run until
-    no book is live.  Every 8th step:
-      * books whose three draws stay inside one pair (known in advance: the draws are RandomSampler's) against a one-book oracle
-        that carries on across the episodes (its buffer rewritten in place with the next day of the same length) -- one such
-        book per pair, so the short days run out of data and the long ones wrap the ring;
-      * books that change to a day of another length between episodes against a one-book engine given the same days as
-        per-book streams (lob_load_events before every episode: no library, no rec_len)."""
+    no book is live.  Every 8th step, against one-book oracles that carry on across the episodes, each given its book's drawn
+    day through Oracle.set_days (the draws are RandomSampler's, known in advance):
+      * the first book of each day of the first episode, so the short days run out of data and the long ones wrap the ring;
+      * six books that change to a day of another length between episodes."""
     monkeypatch.setenv("LOB_TRACK_RING", "1024")
     B, episodes = 16384, 3
     lengths = [400, 400, 700, 700, 1000, 1000, 1500, 1500]
@@ -189,30 +195,27 @@ def test_library_at_scale_ring_mode(monkeypatch, algo):
     # the first draw of 16 384 consecutive seeds is one or two neighbouring days for every book (minstd_rand0's first value is
     # 16807 x seed): it is drawn and replaced before the first reset, the three episodes play draws 2-4
     draws = np.array([days_ref.book_days(p.seed, b, len(days), episodes + 1) for b in range(B)])[:, 1:]
-    pair = draws // 2
+    lib = ol.DayLibrary(days)
     steady = {}
-    for k in range(4):   # the first book of each pair that stays in it
-        books = np.nonzero((pair == k).all(axis=1))[0]
+    for k in range(len(days)):   # the first book of each day of the first episode
+        books = np.nonzero(draws[:, 0] == k)[0]
         assert len(books), k
         steady[int(books[0])] = k
-    movers = [int(b) for b in np.nonzero(np.ptp(np.array(lengths)[draws], axis=1) > 0)[0][:6]]
+    movers = [int(b) for b in np.nonzero(np.ptp(np.array(lengths)[draws], axis=1) > 0)[0] if int(b) not in steady][:6]
     assert len(movers) == 6
     eng = engine.Engine(p, B)
     eng.load_days(days)
     eng.days_select(abi.DAYS_RANDOM, 0, len(days))   # (the correlated first draw, replaced below before any reset)
     orcs = {b: ol.Oracle(params(algo=algo, mem=1 << 12, first_book=b), days[draws[b, 0]][None].copy()) for b in steady}
-    ones = {b: engine.Engine(params(algo=algo, mem=1 << 12, first_book=b), 1) for b in movers}
+    ones = {b: ol.Oracle(params(algo=algo, mem=1 << 12, first_book=b), days[draws[b, 0]][None].copy()) for b in movers}
     for ep in range(episodes):
         eng.days_select(abi.DAYS_RANDOM, 0, len(days))
         eng.reset()
         d = eng.days()
         np.testing.assert_array_equal(d, draws[:, ep])
-        for b, o in orcs.items():
+        for b, o in list(orcs.items()) + list(ones.items()):
             if ep:
-                o.records[0][...] = days[d[b]]        # (same length: the oracle reads this buffer in place)
-            o.reset()
-        for b, o in ones.items():
-            o.load_events(days[d[b]][None])
+                o.set_days(*lib.of(d[b:b + 1]))
             o.reset()
         steps = 0
         while eng.counters()[2] > 0:
@@ -227,9 +230,7 @@ def test_library_at_scale_ring_mode(monkeypatch, algo):
             for b, o in orcs.items():
                 compare_book(ev, b, o, "episode %d step %d book %d" % (ep, steps, b))
             for b, o in ones.items():
-                d1 = dumps_to_np(o.get_books())
-                for name in d1.dtype.names:
-                    assert np.array_equal(d1[name][0], ev["books"][name][b]), (ep, steps, b, name)
+                compare_book(ev, b, o, "episode %d step %d mover %d" % (ep, steps, b))
         eb = ev["books"]
         short = np.array(lengths)[d] == 400
         assert (eb["terminal"][short] == 2).all(), "the 400-event days run out of data"
