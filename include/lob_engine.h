@@ -356,6 +356,44 @@ int lob_clear_inventory(lob_engine* e);
 int lob_get_book(lob_engine* e, int32_t book, lob_book_dump* out);
 int lob_get_books(lob_engine* e, int32_t first, int32_t n, lob_book_dump* out);
 
+/* ---- vector-env interface: step and observe without the host ---------------
+ * The environment face above (lob_step + lob_get_state / lob_get_reward / lob_get_terminal) for a policy that lives on the
+ * GPU: actions are read from device memory, the observations are written to device memory, and everything is enqueued on
+ * the engine's stream (lob_stream) -- no host read of the actions, no allocation, no copy to or from the host and no
+ * synchronisation per step.  It stands in for the same members of environment::Base (include/environment/base.h:117-151:
+ * performAction, getState, getReward, isTerminal) inside the loop of Runner::RunEpisode (src/experiment/serial.cpp:18-34:
+ * `while (!env.isTerminal()) _step()`).
+ *   lob_vec_out: where the results go, all DEVICE pointers on the engine's GPU, written in stream order; a NULL member is
+ * skipped.  After either call
+ *     terminal[b] = what lob_get_terminal reports at that moment; n_live = the number of zeros among them;
+ *     a book with stepped == 1: obs and reward are bit for bit what lob_get_state / lob_get_reward return right after;
+ *     every other book: reward 0.0 (lob_vec_step), obs = the state of its last completed step, or of the reset -- the
+ *     vector its rl::State last took from getState().  Wherever terminal != 2 that is lob_get_state's row as well.
+ *   lob_vec_step: performAction(dev_actions[b]) for every book that is live at entry (terminal == 0) -- the runner's
+ * `while (!env.isTerminal())`.  A book that is over keeps its state, stepped 0.  A step that runs out of data leaves
+ * terminal == 2 and stepped == 0, as with lob_step.  WHERE lob_step DIFFERS: lob_step steps every book with done != 2,
+ * also one whose session is over (terminal == 1), and refuses the whole call for one action out of range.  Here an action
+ * outside [0, LOB_N_ACTIONS) is never used as an index: that book is not stepped in this call (state untouched, stepped 0)
+ * and the entry is counted in a device word of the engine's until lob_vec_status reads it (every out-of-range entry of
+ * dev_actions counts, whether or not its book is live).  The step log gets the row of a book stepped here exactly as from
+ * lob_step, and a ring-mode track is refilled on its schedule.  LOB_ESTATE before the first lob_reset and between
+ * lob_td_step_begin and lob_td_step_end; LOB_EINVAL for a NULL engine, dev_actions or out.
+ *   lob_vec_observe: the same outputs without a step (after lob_reset, after lob_clear_inventory): stepped is written 0,
+ * reward is what lob_get_reward returns, obs is lob_get_state's row wherever terminal != 2.
+ *   lob_vec_status: the one call of this interface that waits.  It synchronises the stream once and returns what the other
+ * entry points report after their steps (LOB_EDATA and its message); otherwise LOB_EINVAL if any action was out of range
+ * since the last call.  *n_bad_actions (may be NULL) gets that count, and the word is cleared; lob_reset clears it too. */
+typedef struct lob_vec_out {      /* all DEVICE pointers on the engine's GPU; any may be NULL = not wanted */
+    float*   obs;                 /* [n_books][n_vars] row-major: getState()                        */
+    double*  reward;              /* [n_books]: getReward() of a stepped book, 0.0 otherwise        */
+    uint8_t* terminal;            /* [n_books]: 0 / 1 / 2 as lob_get_terminal                       */
+    int32_t* stepped;             /* [n_books]: 1 where this call ran a performAction to its end    */
+    int32_t* n_live;              /* one word: books with terminal == 0 after the call              */
+} lob_vec_out;
+int lob_vec_step(lob_engine* e, const int32_t* dev_actions, const lob_vec_out* out);
+int lob_vec_observe(lob_engine* e, const lob_vec_out* out);
+int lob_vec_status(lob_engine* e, int64_t* n_bad_actions);
+
 /* ---- episode statistics of the whole batch ---------------------------------
  * What the reference logs about ONE environment after an episode -- the `training_log` row of Runner::RunEpisode
  * (src/experiment/serial.cpp:81-88: getEpisodeReward, getEpisodePnL, total_ticks), Base::writeStats and getTotalTransactions

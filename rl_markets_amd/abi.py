@@ -133,6 +133,12 @@ class StepRow(C.Structure):
                 ("ask_level", C.c_int32), ("bid_level", C.c_int32)]
 
 
+class VecOut(C.Structure):
+    """lob_vec_out: where lob_vec_step / lob_vec_observe write, five DEVICE addresses (0 = not wanted)."""
+    _fields_ = [("obs", C.c_void_p), ("reward", C.c_void_p), ("terminal", C.c_void_p), ("stepped", C.c_void_p),
+                ("n_live", C.c_void_p)]
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LOB_ENGINE_LIB: an experiment build of the same library (tools/exp_prof.py, tools/exp_variants.sh)
 LIB_PATH = os.environ.get("LOB_ENGINE_LIB") or os.path.join(_HERE, "csrc", "liblob_engine.so")
@@ -198,6 +204,9 @@ def load():
         "lob_step_log_enable": (C.c_int, [vp, vp, C.c_int32, C.c_int32]),
         "lob_step_log_counts": (C.c_int, [vp, vp, vp]),
         "lob_step_log_read": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]),
+        "lob_vec_step": (C.c_int, [vp, vp, P(VecOut)]),
+        "lob_vec_observe": (C.c_int, [vp, P(VecOut)]),
+        "lob_vec_status": (C.c_int, [vp, P(C.c_int64)]),
         "lob_td_step": (C.c_int, [vp, C.c_int32]),
         "lob_td_step_begin": (C.c_int, [vp]),
         "lob_td_split_supported": (C.c_int, [vp]),

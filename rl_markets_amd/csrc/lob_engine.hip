@@ -198,6 +198,7 @@ struct lob_engine {
     bool lib_pending = false;   // a selection waits for the next lob_reset (in set lib_cur ^ 1, or 0)
     Track* track_dev = nullptr;
     i32* actions_dev = nullptr;
+    u64* vec_bad = nullptr;     // lob_vec_step: actions out of range since the last lob_vec_status / lob_reset (one device word)
     i64* cnt_sum = nullptr;     // the striped device counters added up (read_counters)
     lob_book_dump* dump_dev = nullptr;
     int dump_cap = 0;
@@ -328,10 +329,8 @@ void drain_timers(lob_engine* e) {
     }
 }
 
-int check_device_errors(lob_engine* e) {
-    i32 flag = 0;
-    HIPCHK(hipMemcpyAsync(&flag, e->S.error_flag, sizeof flag, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+// LOB_EDATA and its message for a non-zero device error word
+static int device_error_rc(i32 flag) {
     if (flag) {
         std::string m = "device reported a condition on which the reference throws:";
         if (flag & LOB_ERR_BAD_ORDER_PRICE) m += " [order price <= 0]";
@@ -343,6 +342,12 @@ int check_device_errors(lob_engine* e) {
         return LOB_EDATA;
     }
     return LOB_OK;
+}
+int check_device_errors(lob_engine* e) {
+    i32 flag = 0;
+    HIPCHK(hipMemcpyAsync(&flag, e->S.error_flag, sizeof flag, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return device_error_rc(flag);
 }
 
 // The shapes of the switches' values: set at all, to anything; "=0" / "=1" (the first character); a number in [lo, hi]; one of
@@ -696,6 +701,8 @@ int lob_create(const lob_params* p, int32_t n_books, int32_t device, lob_engine*
     alloc(&e->rnd_dev, 2048 + 64);
     S.nzd_terms = e->rnd_dev ? e->rnd_dev + 2048 + LOB_N_ACTIONS : nullptr;  // term[1][.], term[2][.] (filled below)
     alloc(&e->actions_dev, B); alloc(&e->P_dev, 1); alloc(&e->S_dev, 1);
+    alloc(&e->vec_bad, 1);
+    if (rc == LOB_OK && hipMemsetAsync(e->vec_bad, 0, sizeof(u64), e->stream) != hipSuccess) rc = LOB_EHIP;
     if (rc == LOB_OK) { S.self = e->S_dev; memset(&e->S_pushed, 0xff, sizeof(DevState)); }
     if (rc == LOB_OK) rc = push_params(e);
     if (rc != LOB_OK) { lob_destroy(e); return rc; }
@@ -1290,6 +1297,7 @@ int lob_reset(lob_engine* e) {
     HIPCHK(hipMemsetAsync(e->S.acc_list_n, 0, 2 * sizeof(i32), e->stream));
     HIPCHK(hipMemsetAsync(e->S.acc_pend, 0, (size_t)e->B, e->stream));
     if (e->S.dir_list_n) HIPCHK(hipMemsetAsync(e->S.dir_list_n, 0, 2 * sizeof(i32), e->stream));
+    HIPCHK(hipMemsetAsync(e->vec_bad, 0, sizeof(u64), e->stream));   // (lob_vec_step's count of bad actions starts again)
     if (e->slog_n) {   // the step log holds the episode that starts here (its rows need no clearing: the counts say which exist)
         HIPCHK(hipMemsetAsync(e->slog_cnt, 0, 2 * (size_t)e->slog_n * sizeof(i32), e->stream));
         e->slog_armed = true;
@@ -1380,6 +1388,79 @@ int lob_step(lob_engine* e, const int32_t* host_actions) {
     maybe_refill_track(e);
     HIPCHK(hipGetLastError());
     return check_device_errors(e);
+}
+
+// ---- vector-env interface (include/lob_engine.h lob_vec_*; lob_tu_vec.hip) ----
+static VecSrc vec_src(lob_engine* e) {
+    VecSrc s;
+    s.hdr = e->S.hdr; s.done = e->S.done; s.time_ms = e->S.time_ms; s.vars = e->S.vars;
+    s.open_ms = e->P.open_ms; s.close_ms = e->P.close_ms; s.B = e->B; s.V = e->P.V;
+    s.n_bad = e->vec_bad;
+    return s;
+}
+static int vec_entry(lob_engine* e, const lob_vec_out* out, const char* who) {
+    if (!e || !out) { lob_set_error(std::string(who) + ": NULL argument"); return LOB_EINVAL; }
+    int rc = need_reset(e, who);
+    if (rc) return rc;
+    return not_mid_step(e, who);
+}
+
+// lob_step with the actions read, checked and armed on the device and the observation written there: four launches (five with the
+// step log on) and two small memsets on the engine's stream, and the call returns.
+int lob_vec_step(lob_engine* e, const int32_t* dev_actions, const lob_vec_out* out) {
+    if (!dev_actions) { lob_set_error("lob_vec_step: NULL argument"); return LOB_EINVAL; }
+    int rc = vec_entry(e, out, "lob_vec_step");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipMemsetAsync(e->S.mk_count, 0, 2 * sizeof(i32), e->stream));  // claims of this step go on a fresh list (nobody evaluates it)
+    if (out->n_live) HIPCHK(hipMemsetAsync(out->n_live, 0, sizeof(i32), e->stream));
+    e->step_id++;
+    e->hits_ok = false;
+    const VecSrc s = vec_src(e);
+    {
+        TimedLaunch t(e, "vec_actions_kernel");
+        lobk_vec_actions(e->stream, s, dev_actions);
+    }
+    {
+        TimedLaunch t(e, "env_kernel");
+        launch_env(e, e->stream, (const i32*)nullptr, 0, 0, e->B, 0);   // (no action array: go = h.stepped != 0, as armed above)
+    }
+    launch_step_log(e);
+    {
+        TimedLaunch t(e, "vec_observe_kernel");
+        lobk_vec_observe(e->stream, false, true, s, (const DevParams*)e->P_dev, e->S, *out);
+    }
+    maybe_refill_track(e);
+    HIPCHK(hipGetLastError());
+    return LOB_OK;
+}
+
+int lob_vec_observe(lob_engine* e, const lob_vec_out* out) {
+    int rc = vec_entry(e, out, "lob_vec_observe");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    if (out->n_live) HIPCHK(hipMemsetAsync(out->n_live, 0, sizeof(i32), e->stream));
+    {
+        TimedLaunch t(e, "vec_observe_derive_kernel", nullptr, true);
+        lobk_vec_observe(e->stream, true, false, vec_src(e), (const DevParams*)e->P_dev, e->S, *out);
+    }
+    HIPCHK(hipGetLastError());
+    return LOB_OK;
+}
+
+int lob_vec_status(lob_engine* e, int64_t* n_bad_actions) {
+    if (!e) { lob_set_error("lob_vec_status: NULL engine"); return LOB_EINVAL; }
+    HIPCHK(hipSetDevice(e->device));
+    i32 flag = 0;
+    u64 bad = 0;
+    HIPCHK(hipMemcpyAsync(&flag, e->S.error_flag, sizeof flag, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(&bad, e->vec_bad, sizeof bad, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemsetAsync(e->vec_bad, 0, sizeof(u64), e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (n_bad_actions) *n_bad_actions = (int64_t)bad;
+    if (flag) return device_error_rc(flag);
+    if (bad) { lob_set_error("lob_vec_step: " + std::to_string(bad) + " action(s) out of range since the last lob_vec_status; those books were not stepped"); return LOB_EINVAL; }
+    return LOB_OK;
 }
 
 int lob_get_state(lob_engine* e, float* host_out) {

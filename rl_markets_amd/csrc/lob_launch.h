@@ -1,6 +1,6 @@
-// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is six
+// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is seven
 // .hip files built in parallel: lob_engine.hip -- the C ABI's host side and the update / memo / trace kernels --, lob_tu_env.hip,
-// lob_tu_prepass.hip, lob_tu_learn.hip, lob_tu_stats.hip, lob_tu_steplog.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
+// lob_tu_prepass.hip, lob_tu_learn.hip, lob_tu_stats.hip, lob_tu_steplog.hip, lob_tu_vec.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
 // lob_engine.hip used when it held the launches itself.  Kernels measured and lost (NOTES.md "Round 4") are only compiled with
 // -DLOB_EXPERIMENTS (tools/exp_variants.sh); a product build answers LOB_EXPERIMENTS-only requests with the product kernel.
 #ifndef LOB_LAUNCH_H
@@ -82,6 +82,26 @@ void lobk_step_log(hipStream_t st, const StepLogSrc& s);
 // out[(j - first_sel) * n_rows + (k - first_row)] = row k of selected book j, 96 zero bytes beyond the book's stored count
 void lobk_step_log_gather(hipStream_t st, const lob_step_row* rows, const i32* n_stored, int n_sel_all, int first_sel, int n_sel, int first_row,
                           int n_rows, lob_step_row* out);
+
+// ---- lob_tu_vec.hip ----
+// What the vector-env interface (include/lob_engine.h lob_vec_*) reads and arms, as kernel arguments (the DevState does not grow):
+// the books' step headers, the two field arrays of lob_get_terminal, the state vectors with their slot-2 copy of the latest
+// getState(), the two session times of is_open and the engine's word that counts actions out of range.
+#define LOB_VEC_BLOCK 256
+struct VecSrc {
+    LHdr* hdr;
+    const i32 *done, *time_ms;
+    const f32* vars;           // [B][3][16]
+    i64 open_ms, close_ms;
+    i32 B, V;
+    u64* n_bad;
+};
+// vec_actions_kernel: LHdr::action / stepped of every book from the caller's device actions, for env_kernel's `go = h.stepped != 0`
+void lobk_vec_actions(hipStream_t st, const VecSrc& s, const i32* dev_actions);
+// vec_observe_kernel (`after_step`: behind lobk_env, stepped / reward from the headers; obs from slot 2 either way) or, `derive`,
+// vec_observe_derive_kernel: obs and reward evaluated as get_state_kernel does (lob_vec_observe).  out.n_live must have been cleared
+// on the stream.
+void lobk_vec_observe(hipStream_t st, bool derive, bool after_step, const VecSrc& s, const DevParams* Pd, const DevState& S, const lob_vec_out& out);
 
 // ---- lob_tu_learn.hip ----
 // learn_q_pair_kernel / learn_q_lane_kernel<algo, vt, tr>: vt = 8 when the state has eight variables (else 0)

@@ -270,6 +270,29 @@ class Engine:
         self._check(self.lib.lob_step_log_read(self.h, first_sel, n_sel, first_row, n_rows, _ptr(out)))
         return out[:max(n_sel, 0), :max(n_rows, 0)]
 
+    # ---- vector-env interface: raw device addresses in, nothing waits (rl_markets_amd/vec_env.py is the torch-facing wrapper) ----
+    def vec_step(self, actions_ptr, out):
+        """lob_vec_step: performAction(actions[b]) for every live book, actions read from the int32[n_books] device buffer at
+        `actions_ptr`, results written to the device buffers of `out` (abi.VecOut) -- enqueued on the engine's stream."""
+        self._check(self.lib.lob_vec_step(self.h, C.c_void_p(actions_ptr), C.byref(out)))
+
+    def vec_observe(self, out):
+        """lob_vec_observe: the outputs of vec_step without a step (after reset(), after clear_inventory())."""
+        self._check(self.lib.lob_vec_observe(self.h, C.byref(out)))
+
+    def vec_status(self):
+        """lob_vec_status: waits for the stream once; (return code, actions out of range since the last call).  LOB_EDATA is
+        raised as every other entry point raises it; LOB_EINVAL -- bad actions -- is returned, with the count."""
+        n = C.c_int64(0)
+        rc = self.lib.lob_vec_status(self.h, C.byref(n))
+        if rc not in (abi.LOB_OK, abi.LOB_EINVAL):
+            self._check(rc)
+        return rc, int(n.value)
+
+    def lob_stream(self):
+        """lob_stream: the engine's hipStream_t as an integer."""
+        return int(self.lib.lob_stream(self.h) or 0)
+
     # ---- learner ----
     def td_step(self, n=1):
         self._check(self.lib.lob_td_step(self.h, n))

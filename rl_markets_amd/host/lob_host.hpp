@@ -302,6 +302,16 @@ public:
         return true;
     }
     bool performAction(int action) { return performAction(std::vector<int32_t>(B_, action)); }
+    // The same for a policy that lives on the GPU (lob_vec_step / lob_vec_observe / lob_vec_status, include/lob_engine.h): actions
+    // and outputs are DEVICE memory, the calls are enqueued on the engine's stream and return; nothing is cached on the host.
+    // status_device is the one call that waits; false = actions were out of range since the last call (*n_bad says how many).
+    void step_device(const int32_t* dev_actions, const lob_vec_out& out) { check(lob_vec_step(e_, dev_actions, &out), "step_device"); invalidate(); }
+    void observe_device(const lob_vec_out& out) { check(lob_vec_observe(e_, &out), "observe_device"); }
+    bool status_device(int64_t* n_bad = nullptr) {
+        const int rc = lob_vec_status(e_, n_bad);
+        if (rc != LOB_EINVAL) check(rc, "status_device");
+        return rc == LOB_OK;
+    }
     void getState(std::vector<float>& out, int book = 0) {  // APPENDS n_vars floats (base.h:125)
         refresh();
         out.insert(out.end(), state_cache_.begin() + (size_t)book * p_.n_vars, state_cache_.begin() + (size_t)(book + 1) * p_.n_vars);

@@ -1,0 +1,75 @@
+"""VecEnv: the books of one engine as a batched environment for a policy that lives in torch, on the engine's GPU.
+
+    import torch                                   # before the engine library is loaded: one HIP runtime per process
+    from rl_markets_amd import engine
+    from rl_markets_amd.vec_env import VecEnv
+
+    env = VecEnv(eng)                              # eng: an engine.Engine with its events loaded
+    obs = env.reset()                              # f32 [B, V], on the device
+    while int(env.n_live) > 0:                     # (the one host read of the loop: ask every few steps, or not at all)
+        actions = policy(obs).argmax(1).to(torch.int32)
+        obs, reward, terminal, stepped = env.step(actions)
+
+step() reads the actions from the tensor's device memory and writes into five persistent tensors (lob_vec_step,
+include/lob_engine.h): no copy to or from the host and no synchronisation.  The engine runs on a stream of its own; it is made
+to wait for torch's current stream before the call (the actions are ready) and torch's current stream for the engine's after it
+(the outputs are ready), both on the device.  The tensors are overwritten by the next step(): clone what must be kept.
+
+torch is imported by this module only; nothing else under rl_markets_amd needs it."""
+import torch
+
+from . import abi
+
+
+class VecEnv:
+    def __init__(self, eng):
+        self.eng = eng
+        self.B, self.V = eng.B, eng.V
+        dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self.obs = torch.zeros((self.B, self.V), dtype=torch.float32, device=dev)
+        self.reward = torch.zeros(self.B, dtype=torch.float64, device=dev)
+        self.terminal = torch.zeros(self.B, dtype=torch.uint8, device=dev)
+        self.stepped = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.n_live = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.out = abi.VecOut(self.obs.data_ptr(), self.reward.data_ptr(), self.terminal.data_ptr(), self.stepped.data_ptr(),
+                              self.n_live.data_ptr())
+        self.stream = torch.cuda.ExternalStream(eng.lob_stream(), device=dev)
+        self.bad_actions = 0
+        # (the zero fills above ran on torch's stream: the engine's first write must come after them)
+        self.stream.wait_stream(torch.cuda.current_stream(dev))
+
+    def _call(self, fn, *args):
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)      # what torch has enqueued so far (the actions) comes first
+        fn(*args, self.out)
+        cur.wait_stream(self.stream)      # what torch enqueues from here on sees the outputs
+        return cur
+
+    def reset(self):
+        """lob_reset (which waits for its own result, as it always has) and the first observation."""
+        self.eng.reset()
+        return self.observe()
+
+    def observe(self):
+        """The observation without a step: after reset(), after the engine's clear_inventory()."""
+        self._call(self.eng.vec_observe)
+        return self.obs
+
+    def step(self, actions):
+        """actions: int32 [B] on the engine's device.  Returns (obs, reward, terminal, stepped), the persistent tensors."""
+        if actions.dtype != torch.int32 or not actions.is_cuda or actions.shape != (self.B,) or not actions.is_contiguous():
+            raise ValueError("VecEnv.step: actions must be a contiguous int32 CUDA tensor of shape (%d,)" % self.B)
+        cur = self._call(self.eng.vec_step, actions.data_ptr())
+        # The engine reads `actions` on its own stream, and the caching allocator must not hand the block out again before
+        # that.  `cur` now waits for the engine's stream, so whatever follows on `cur` follows the read: the block is marked as
+        # used on `cur` (nothing to do where it was allocated there), never on the engine's stream, which the allocator would
+        # record an event on when the tensor is freed -- possibly after Engine.close() has destroyed that stream.
+        actions.record_stream(cur)
+        return self.obs, self.reward, self.terminal, self.stepped
+
+    def status(self):
+        """lob_vec_status: waits once; LOB_OK, or LOB_EINVAL when actions were out of range since the last call (their number
+        is left in .bad_actions).  A malformed event stream raises engine.LobError (LOB_EDATA)."""
+        rc, self.bad_actions = self.eng.vec_status()
+        return rc
