@@ -394,6 +394,50 @@ int lob_vec_step(lob_engine* e, const int32_t* dev_actions, const lob_vec_out* o
 int lob_vec_observe(lob_engine* e, const lob_vec_out* out);
 int lob_vec_status(lob_engine* e, int64_t* n_bad_actions);
 
+/* ---- vector-env interface: the order book itself, written to device memory ---
+ * What a network behind lob_vec_step wants to see beyond the `n_vars` hand-made variables of lob_vec_out::obs: the `depth`
+ * levels of both sides of every book (market::Book's current snapshot, include/market/book.h:34-48) and the agent's own
+ * standing orders, queue positions, inventory and episode sums (the protected members of environment::Base,
+ * include/environment/base.h:39-95) -- until now only reachable through the parity dump lob_get_books (912 bytes per book, to
+ * the host).
+ *   lob_vec_book_out: where the values go, all DEVICE pointers on the engine's GPU, written in stream order; a NULL member is
+ * skipped.  ONE rule: for EVERY book b, whatever its `terminal` value, every written element is the lob_book_dump field that
+ * lob_get_books would report for b at that point of the stream, converted f64 -> f32 and int64 / int32 -> f32 by IEEE
+ * round-to-nearest-even (a NaN stays a NaN); time_ms is copied as int64.
+ *     levels[b][0][l] = (float)ask_px[l]   levels[b][1][l] = (float)ask_vol[l]
+ *     levels[b][2][l] = (float)bid_px[l]   levels[b][3][l] = (float)bid_vol[l]      l < depth (lob_params::depth, not
+ *     LOB_MAX_DEPTH); level 0 is the touch.  Where the dump has price 0.0 (no snapshot yet) price and volume are 0.
+ *     own[b][LOB_OWN_*]: the sixteen dump fields named below, in that order; the order fields of a side without a live order
+ *     are 0, *_order_rem is the order's remaining volume, as in the dump.
+ *   lob_vec_book: enqueued on the engine's stream (lob_stream), returns at once -- no host read, no allocation, no copy and no
+ * synchronisation -- and changes no engine state.  Valid whenever lob_get_books is meaningful: after the first lob_reset, after
+ * lob_vec_step, lob_step, lob_td_step, lob_eval_step and lob_clear_inventory.  LOB_EINVAL for a NULL engine or a NULL out; a
+ * struct whose three members are all NULL is LOB_OK and launches nothing.  LOB_ESTATE before the first lob_reset and between
+ * lob_td_step_begin and lob_td_step_end. */
+#define LOB_VEC_OWN_WORDS 16
+#define LOB_OWN_POSITION 0
+#define LOB_OWN_ASK_HAS_ORDER 1
+#define LOB_OWN_ASK_ORDER_PX 2
+#define LOB_OWN_ASK_ORDER_REM 3
+#define LOB_OWN_ASK_Q_HEAD 4
+#define LOB_OWN_BID_HAS_ORDER 5
+#define LOB_OWN_BID_ORDER_PX 6
+#define LOB_OWN_BID_ORDER_REM 7
+#define LOB_OWN_BID_Q_HEAD 8
+#define LOB_OWN_ASK_QUOTE 9
+#define LOB_OWN_BID_QUOTE 10
+#define LOB_OWN_LAST_ACTION 11
+#define LOB_OWN_PNL_STEP 12
+#define LOB_OWN_EPISODE_PNL 13
+#define LOB_OWN_EPISODE_REWARD 14
+#define LOB_OWN_TOTAL_TICKS 15
+typedef struct lob_vec_book_out {   /* all DEVICE pointers on the engine's GPU; any may be NULL = not wanted */
+    float*   levels;    /* [n_books][4][depth] row-major: plane 0 ask_px, 1 ask_vol, 2 bid_px, 3 bid_vol; level 0 = touch */
+    float*   own;       /* [n_books][LOB_VEC_OWN_WORDS] */
+    int64_t* time_ms;   /* [n_books] */
+} lob_vec_book_out;
+int lob_vec_book(lob_engine* e, const lob_vec_book_out* out);
+
 /* ---- episode statistics of the whole batch ---------------------------------
  * What the reference logs about ONE environment after an episode -- the `training_log` row of Runner::RunEpisode
  * (src/experiment/serial.cpp:81-88: getEpisodeReward, getEpisodePnL, total_ticks), Base::writeStats and getTotalTransactions

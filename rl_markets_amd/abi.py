@@ -139,6 +139,22 @@ class VecOut(C.Structure):
                 ("n_live", C.c_void_p)]
 
 
+# lob_vec_book: the words of VecBookOut.own, in array order (LOB_OWN_*)
+VEC_OWN_WORDS = 16
+(OWN_POSITION, OWN_ASK_HAS_ORDER, OWN_ASK_ORDER_PX, OWN_ASK_ORDER_REM, OWN_ASK_Q_HEAD, OWN_BID_HAS_ORDER, OWN_BID_ORDER_PX,
+ OWN_BID_ORDER_REM, OWN_BID_Q_HEAD, OWN_ASK_QUOTE, OWN_BID_QUOTE, OWN_LAST_ACTION, OWN_PNL_STEP, OWN_EPISODE_PNL, OWN_EPISODE_REWARD,
+ OWN_TOTAL_TICKS) = range(16)
+# the lob_book_dump field behind each word
+OWN_FIELDS = ("position", "ask_has_order", "ask_order_px", "ask_order_rem", "ask_q_head", "bid_has_order", "bid_order_px",
+              "bid_order_rem", "bid_q_head", "ask_quote", "bid_quote", "last_action", "pnl_step", "episode_pnl", "episode_reward",
+              "total_ticks")
+
+
+class VecBookOut(C.Structure):
+    """lob_vec_book_out: where lob_vec_book writes, three DEVICE addresses (0 = not wanted)."""
+    _fields_ = [("levels", C.c_void_p), ("own", C.c_void_p), ("time_ms", C.c_void_p)]
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LOB_ENGINE_LIB: an experiment build of the same library (tools/exp_prof.py, tools/exp_variants.sh)
 LIB_PATH = os.environ.get("LOB_ENGINE_LIB") or os.path.join(_HERE, "csrc", "liblob_engine.so")
@@ -207,6 +223,7 @@ def load():
         "lob_vec_step": (C.c_int, [vp, vp, P(VecOut)]),
         "lob_vec_observe": (C.c_int, [vp, P(VecOut)]),
         "lob_vec_status": (C.c_int, [vp, P(C.c_int64)]),
+        "lob_vec_book": (C.c_int, [vp, P(VecBookOut)]),
         "lob_td_step": (C.c_int, [vp, C.c_int32]),
         "lob_td_step_begin": (C.c_int, [vp]),
         "lob_td_split_supported": (C.c_int, [vp]),

@@ -1463,6 +1463,34 @@ int lob_vec_status(lob_engine* e, int64_t* n_bad_actions) {
     return LOB_OK;
 }
 
+// The order book and the agent's own words of every book into the caller's device buffers (lob_tu_vecbook.hip vec_book_kernel): one
+// launch on the engine's stream, nothing read back, nothing changed.
+int lob_vec_book(lob_engine* e, const lob_vec_book_out* out) {
+    if (!e || !out) { lob_set_error("lob_vec_book: NULL argument"); return LOB_EINVAL; }
+    int rc = need_reset(e, "lob_vec_book");
+    if (rc) return rc;
+    if ((rc = not_mid_step(e, "lob_vec_book"))) return rc;
+    if (!out->levels && !out->own && !out->time_ms) return LOB_OK;
+    HIPCHK(hipSetDevice(e->device));
+    VecBookSrc s;
+    s.records = e->S.records; s.rec_phase = e->S.rec_phase; s.rec_cur = e->S.rec_cur;
+    s.n_events = e->S.n_events; s.Wd = e->P.Wd; s.D = e->P.D;
+    s.w_ask_px = drec_ask_px(e->P.D, e->P.T); s.w_ask_vol = drec_ask_vol(e->P.D, e->P.T);
+    s.w_bid_px = drec_bid_px(e->P.D, e->P.T); s.w_bid_vol = drec_bid_vol(e->P.D, e->P.T);
+    s.position = e->S.position;
+    s.a_osz = e->S.a_osz; s.a_oex = e->S.a_oex; s.a_oqh = e->S.a_oqh; s.b_osz = e->S.b_osz; s.b_oex = e->S.b_oex; s.b_oqh = e->S.b_oqh;
+    s.a_on = e->S.a_on; s.b_on = e->S.b_on; s.last_action = e->S.last_action; s.total_ticks = e->S.total_ticks; s.time_ms = e->S.time_ms;
+    s.a_opx = e->S.a_opx; s.b_opx = e->S.b_opx; s.ask_quote = e->S.ask_quote; s.bid_quote = e->S.bid_quote;
+    s.pnl_step = e->S.pnl_step; s.ep_pnl = e->S.ep_pnl; s.ep_reward = e->S.ep_reward;
+    s.B = e->B;
+    {
+        TimedLaunch t(e, "vec_book_kernel", nullptr, true);
+        lobk_vec_book(e->stream, s, *out);
+    }
+    HIPCHK(hipGetLastError());
+    return LOB_OK;
+}
+
 int lob_get_state(lob_engine* e, float* host_out) {
     int rc = need_reset(e, "lob_get_state");
     if (rc) return rc;

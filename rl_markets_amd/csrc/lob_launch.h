@@ -1,6 +1,6 @@
-// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is seven
+// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is eight
 // .hip files built in parallel: lob_engine.hip -- the C ABI's host side and the update / memo / trace kernels --, lob_tu_env.hip,
-// lob_tu_prepass.hip, lob_tu_learn.hip, lob_tu_stats.hip, lob_tu_steplog.hip, lob_tu_vec.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
+// lob_tu_prepass.hip, lob_tu_learn.hip, lob_tu_stats.hip, lob_tu_steplog.hip, lob_tu_vec.hip, lob_tu_vecbook.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
 // lob_engine.hip used when it held the launches itself.  Kernels measured and lost (NOTES.md "Round 4") are only compiled with
 // -DLOB_EXPERIMENTS (tools/exp_variants.sh); a product build answers LOB_EXPERIMENTS-only requests with the product kernel.
 #ifndef LOB_LAUNCH_H
@@ -102,6 +102,27 @@ void lobk_vec_actions(hipStream_t st, const VecSrc& s, const i32* dev_actions);
 // vec_observe_derive_kernel: obs and reward evaluated as get_state_kernel does (lob_vec_observe).  out.n_live must have been cleared
 // on the stream.
 void lobk_vec_observe(hipStream_t st, bool derive, bool after_step, const VecSrc& s, const DevParams* Pd, const DevState& S, const lob_vec_out& out);
+
+// ---- lob_tu_vecbook.hip ----
+// What lob_vec_book (include/lob_engine.h) reads, as kernel arguments (the DevState does not grow): the event records with the
+// words of a record at which the four level arrays start (the device layout, lob_env.h drec_*: each array 16-byte aligned, `D`
+// words used), the books' current-record word -- dump_kernel takes e.rec_cur from this field array and follows it through
+// EnvCtx::row, i.e. records + (rec_phase[b] or b * n_events, + rec_cur[b]) * Wd; neither the per-book meta nor the track is on that
+// way -- and the environment field arrays of LOB_ENV_FIELDS behind the sixteen words of `own` and time_ms.
+#define LOB_VECBOOK_BLOCK 256
+#define LOB_VECBOOK_BOOKS 64   // books per block (8 lanes per book and pass, two passes): 14 KB of staging, so LDS never bounds the waves per CU
+struct VecBookSrc {
+    const uint32_t* records;   // DevState::records / rec_phase (null: book b's stream starts at record b * n_events)
+    const i64* rec_phase;
+    const i32* rec_cur;
+    i32 n_events, Wd, D;
+    i32 w_ask_px, w_ask_vol, w_bid_px, w_bid_vol;
+    const i64 *position, *a_osz, *a_oex, *a_oqh, *b_osz, *b_oex, *b_oqh;
+    const i32 *a_on, *b_on, *last_action, *total_ticks, *time_ms;
+    const f64 *a_opx, *b_opx, *ask_quote, *bid_quote, *pnl_step, *ep_pnl, *ep_reward;
+    i32 B;
+};
+void lobk_vec_book(hipStream_t st, const VecBookSrc& s, const lob_vec_book_out& out);
 
 // ---- lob_tu_learn.hip ----
 // learn_q_pair_kernel / learn_q_lane_kernel<algo, vt, tr>: vt = 8 when the state has eight variables (else 0)

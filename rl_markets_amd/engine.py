@@ -289,6 +289,12 @@ class Engine:
             self._check(rc)
         return rc, int(n.value)
 
+    def vec_book(self, out):
+        """lob_vec_book: the depth levels of every book, the agent's own sixteen words (abi.OWN_*) and the market time, written to
+        the device buffers of `out` (abi.VecBookOut) -- every value what get_books() reports, as f32; enqueued on the engine's
+        stream."""
+        self._check(self.lib.lob_vec_book(self.h, C.byref(out)))
+
     def lob_stream(self):
         """lob_stream: the engine's hipStream_t as an integer."""
         return int(self.lib.lob_stream(self.h) or 0)

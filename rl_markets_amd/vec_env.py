@@ -10,6 +10,11 @@
         actions = policy(obs).argmax(1).to(torch.int32)
         obs, reward, terminal, stepped = env.step(actions)
 
+VecEnv(eng, book=True) also keeps the order book itself on the device (lob_vec_book): .levels f32 [B, 4, D] -- plane 0 ask prices, 1 ask
+volumes, 2 bid prices, 3 bid volumes, level 0 the touch --, .own f32 [B, 16] (abi.OWN_*: inventory, the standing orders and their
+queue positions, quotes, last action, PnL and reward sums, ticks) and .time_ms i64 [B], raw values as get_books() reports them.
+They are attributes, refreshed behind every step() / observe() / reset() and ready wherever `obs` is.
+
 step() reads the actions from the tensor's device memory and writes into five persistent tensors (lob_vec_step,
 include/lob_engine.h): no copy to or from the host and no synchronisation.  The engine runs on a stream of its own; it is made
 to wait for torch's current stream before the call (the actions are ready) and torch's current stream for the engine's after it
@@ -22,7 +27,7 @@ from . import abi
 
 
 class VecEnv:
-    def __init__(self, eng):
+    def __init__(self, eng, book=False):
         self.eng = eng
         self.B, self.V = eng.B, eng.V
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -34,6 +39,12 @@ class VecEnv:
         self.n_live = torch.zeros(1, dtype=torch.int32, device=dev)
         self.out = abi.VecOut(self.obs.data_ptr(), self.reward.data_ptr(), self.terminal.data_ptr(), self.stepped.data_ptr(),
                               self.n_live.data_ptr())
+        self.book_out = None
+        if book:
+            self.levels = torch.zeros((self.B, 4, eng.params.depth), dtype=torch.float32, device=dev)
+            self.own = torch.zeros((self.B, abi.VEC_OWN_WORDS), dtype=torch.float32, device=dev)
+            self.time_ms = torch.zeros(self.B, dtype=torch.int64, device=dev)
+            self.book_out = abi.VecBookOut(self.levels.data_ptr(), self.own.data_ptr(), self.time_ms.data_ptr())
         self.stream = torch.cuda.ExternalStream(eng.lob_stream(), device=dev)
         self.bad_actions = 0
         # (the zero fills above ran on torch's stream: the engine's first write must come after them)
@@ -43,6 +54,8 @@ class VecEnv:
         cur = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(cur)      # what torch has enqueued so far (the actions) comes first
         fn(*args, self.out)
+        if self.book_out is not None:
+            self.eng.vec_book(self.book_out)   # (right behind it on the engine's stream: the book as the step left it)
         cur.wait_stream(self.stream)      # what torch enqueues from here on sees the outputs
         return cur
 
