@@ -438,6 +438,42 @@ typedef struct lob_vec_book_out {   /* all DEVICE pointers on the engine's GPU; 
 } lob_vec_book_out;
 int lob_vec_book(lob_engine* e, const lob_vec_book_out* out);
 
+/* ---- vector-env interface: the last K event records of every book, written to device memory ---
+ * What a network over a WINDOW of book updates wants (a DeepLOB-style input: the last K events x 4 * depth level values, and the
+ * trades that came with them): for every book the K most recent records of its own event stream, ending with the record its
+ * current snapshot comes from -- the data::MarketDepthRecord (time, ask / bid prices and volumes per level) and the
+ * data::TimeAndSalesRecord (trade prices and volumes) of each of the last K events, as one Intraday::NextState consumes them.
+ * Between two agent steps a book consumes a variable number of events, so stacking successive lob_vec_book outputs does not give
+ * this window; the records themselves are resident in device memory and are read there.
+ *   lob_vec_hist_out: where the values go, all DEVICE pointers on the engine's GPU, written in stream order; a NULL member is
+ * skipped.  ONE rule, for EVERY book b, whatever its `terminal` value.  Let r = rec[b], the record the book's current snapshot
+ * comes from -- the one lob_get_books reads ask_px / ask_vol / bid_px / bid_vol from (cursor - 1 wherever terminal != 2); -1 when
+ * the book has no snapshot.
+ *     slot k (0 <= k < K) holds record r - (K - 1 - k) OF THAT BOOK'S STREAM: the n_events records loaded for it, the n_events
+ *     records from phase[b] of a replayed stream (lob_load_events_shared), the records of the day it is playing (lob_load_days);
+ *     a slot whose record index is negative is all zeros -- levels, trades and time --, never a record of the previous book, of the
+ *     previous day or of the replayed stream before phase[b];
+ *     levels[b][k][0][l] = ask_px[l]   levels[b][k][1][l] = ask_vol[l]   levels[b][k][2][l] = bid_px[l]   levels[b][k][3][l] =
+ *     bid_vol[l], l < depth, level 0 the touch;  trades[b][k][0][i] = trade_px[i]   trades[b][k][1][i] = trade_vol[i], i <
+ *     max_trades;  time_ms[b][k] = word 0 of the record.  Prices are the record's f32 bit for bit; volumes go int32 -> f32 by IEEE
+ *     round-to-nearest-even; an empty trade slot is whatever the record holds (volume 0);
+ *     n_valid[b] = min(K, r + 1), the slots k >= K - n_valid[b] that hold a record; 0 when the book has no snapshot.
+ *   Every element of every non-NULL tensor is written on every call.  Slot K - 1 of `levels` is lob_vec_book's levels[b] for every
+ * book with r >= 0.  K is the caller's, per call: any 1 <= K <= LOB_MAX_HISTORY is valid on any stream, also K > n_events.
+ *   lob_vec_history: enqueued on the engine's stream (lob_stream), returns at once -- no host read, no allocation, no copy and no
+ * synchronisation -- and changes no engine state.  Valid whenever lob_get_books is meaningful (see lob_vec_book).  LOB_EINVAL for a
+ * NULL engine, a NULL out or K outside [1, LOB_MAX_HISTORY]; a struct whose five members are all NULL is LOB_OK and launches
+ * nothing.  LOB_ESTATE before the first lob_reset and between lob_td_step_begin and lob_td_step_end. */
+#define LOB_MAX_HISTORY 128
+typedef struct lob_vec_hist_out {   /* all DEVICE pointers on the engine's GPU; any may be NULL = not wanted */
+    float*   levels;    /* [n_books][K][4][depth]: planes ask_px, ask_vol, bid_px, bid_vol; level 0 = touch */
+    float*   trades;    /* [n_books][K][2][max_trades]: plane 0 trade_px, plane 1 trade_vol                 */
+    int32_t* time_ms;   /* [n_books][K]: word 0 of the record                                             */
+    int32_t* n_valid;   /* [n_books]: min(K, rec + 1); 0 when the book has no snapshot                      */
+    int32_t* rec;       /* [n_books]: index, within the book's own stream, of the record in slot K-1; -1 = none */
+} lob_vec_hist_out;
+int lob_vec_history(lob_engine* e, int32_t K, const lob_vec_hist_out* out);
+
 /* ---- episode statistics of the whole batch ---------------------------------
  * What the reference logs about ONE environment after an episode -- the `training_log` row of Runner::RunEpisode
  * (src/experiment/serial.cpp:81-88: getEpisodeReward, getEpisodePnL, total_ticks), Base::writeStats and getTotalTransactions

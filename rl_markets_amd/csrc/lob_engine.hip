@@ -1491,6 +1491,29 @@ int lob_vec_book(lob_engine* e, const lob_vec_book_out* out) {
     return LOB_OK;
 }
 
+// The last K event records of every book into the caller's device buffers (lob_tu_vechist.hip vec_hist_kernel): one launch on the
+// engine's stream, nothing read back, nothing changed.  e->S.records as it is now: a stream handed over by lob_stage_events is followed.
+int lob_vec_history(lob_engine* e, int32_t K, const lob_vec_hist_out* out) {
+    if (!e || !out) { lob_set_error("lob_vec_history: NULL argument"); return LOB_EINVAL; }
+    if (K < 1 || K > LOB_MAX_HISTORY) { lob_set_error("lob_vec_history: K = " + std::to_string(K) + " is outside [1, " + std::to_string(LOB_MAX_HISTORY) + "]"); return LOB_EINVAL; }
+    int rc = need_reset(e, "lob_vec_history");
+    if (rc) return rc;
+    if ((rc = not_mid_step(e, "lob_vec_history"))) return rc;
+    if (!out->levels && !out->trades && !out->time_ms && !out->n_valid && !out->rec) return LOB_OK;
+    HIPCHK(hipSetDevice(e->device));
+    VecHistSrc s;
+    s.records = e->S.records; s.rec_phase = e->S.rec_phase; s.rec_cur = e->S.rec_cur; s.rec_len = e->S.rec_len;
+    s.n_events = e->S.n_events; s.Wd = e->P.Wd; s.D = e->P.D; s.T = e->P.T; s.B = e->B;
+    s.w_ask_px = drec_ask_px(e->P.D, e->P.T); s.w_ask_vol = drec_ask_vol(e->P.D, e->P.T);
+    s.w_bid_px = drec_bid_px(e->P.D, e->P.T); s.w_bid_vol = drec_bid_vol(e->P.D, e->P.T); s.w_trades = drec_trades(e->P.D, e->P.T);
+    {
+        TimedLaunch t(e, "vec_hist_kernel", nullptr, true);
+        lobk_vec_history(e->stream, s, K, *out);
+    }
+    HIPCHK(hipGetLastError());
+    return LOB_OK;
+}
+
 int lob_get_state(lob_engine* e, float* host_out) {
     int rc = need_reset(e, "lob_get_state");
     if (rc) return rc;

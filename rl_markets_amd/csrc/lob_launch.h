@@ -1,6 +1,6 @@
-// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is eight
+// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is nine
 // .hip files built in parallel: lob_engine.hip -- the C ABI's host side and the update / memo / trace kernels --, lob_tu_env.hip,
-// lob_tu_prepass.hip, lob_tu_learn.hip, lob_tu_stats.hip, lob_tu_steplog.hip, lob_tu_vec.hip, lob_tu_vecbook.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
+// lob_tu_prepass.hip, lob_tu_learn.hip, lob_tu_stats.hip, lob_tu_steplog.hip, lob_tu_vec.hip, lob_tu_vecbook.hip, lob_tu_vechist.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
 // lob_engine.hip used when it held the launches itself.  Kernels measured and lost (NOTES.md "Round 4") are only compiled with
 // -DLOB_EXPERIMENTS (tools/exp_variants.sh); a product build answers LOB_EXPERIMENTS-only requests with the product kernel.
 #ifndef LOB_LAUNCH_H
@@ -123,6 +123,23 @@ struct VecBookSrc {
     i32 B;
 };
 void lobk_vec_book(hipStream_t st, const VecBookSrc& s, const lob_vec_book_out& out);
+
+// ---- lob_tu_vechist.hip ----
+// What lob_vec_history (include/lob_engine.h) reads, as kernel arguments (the DevState does not grow): the event records, the first
+// record of every book's stream (rec_phase, or b * n_events), the books' current-record word, the length of every book's stream
+// (rec_len, or n_events: the bound of the window's last record) and the words of a record at which its arrays start (the device
+// layout, lob_env.h drec_*: header quad, four level arrays of D words padded to quads, T interleaved (price, volume) pairs).
+#define LOB_VECHIST_BLOCK 256
+#define LOB_VECHIST_ROWS 64   // (book, slot) rows per block: 15 KB of staging for D = 10, T = 8, so LDS never bounds the waves per CU
+struct VecHistSrc {
+    const uint32_t* records;   // DevState::records / rec_phase (null: book b's stream starts at record b * n_events)
+    const i64* rec_phase;
+    const i32* rec_cur;
+    const i32* rec_len;        // DevState::rec_len (null: every stream has n_events records)
+    i32 n_events, Wd, D, T, B;
+    i32 w_ask_px, w_ask_vol, w_bid_px, w_bid_vol, w_trades;
+};
+void lobk_vec_history(hipStream_t st, const VecHistSrc& s, int K, const lob_vec_hist_out& out);
 
 // ---- lob_tu_learn.hip ----
 // learn_q_pair_kernel / learn_q_lane_kernel<algo, vt, tr>: vt = 8 when the state has eight variables (else 0)

@@ -295,6 +295,13 @@ class Engine:
         stream."""
         self._check(self.lib.lob_vec_book(self.h, C.byref(out)))
 
+    def vec_history(self, K, out):
+        """lob_vec_history: the last K (1 .. abi.MAX_HISTORY) event records of every book -- levels f32 [B, K, 4, depth], trades f32
+        [B, K, 2, max_trades], time_ms i32 [B, K], oldest first, the record behind the current snapshot in slot K - 1, zeros before
+        the start of the book's stream --, n_valid and rec i32 [B], written to the device buffers of `out` (abi.VecHistOut);
+        enqueued on the engine's stream."""
+        self._check(self.lib.lob_vec_history(self.h, int(K), C.byref(out)))
+
     def lob_stream(self):
         """lob_stream: the engine's hipStream_t as an integer."""
         return int(self.lib.lob_stream(self.h) or 0)

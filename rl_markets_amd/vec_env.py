@@ -15,6 +15,12 @@ volumes, 2 bid prices, 3 bid volumes, level 0 the touch --, .own f32 [B, 16] (ab
 queue positions, quotes, last action, PnL and reward sums, ticks) and .time_ms i64 [B], raw values as get_books() reports them.
 They are attributes, refreshed behind every step() / observe() / reset() and ready wherever `obs` is.
 
+VecEnv(eng, history=K) keeps the last K event records of every book on the device (lob_vec_history, 1 <= K <= abi.MAX_HISTORY):
+.hist_levels f32 [B, K, 4, D] (the planes of .levels), .hist_trades f32 [B, K, 2, T] (plane 0 trade prices, 1 trade volumes),
+.hist_time_ms i32 [B, K], oldest first with the record behind the current snapshot in slot K - 1 and zeros before the start of the
+book's stream; .hist_valid i32 [B] counts the slots that hold a record and .hist_rec i32 [B] is the index of the newest one within
+the book's stream (-1: none).  Refreshed like the book tensors; the two options are independent.
+
 step() reads the actions from the tensor's device memory and writes into five persistent tensors (lob_vec_step,
 include/lob_engine.h): no copy to or from the host and no synchronisation.  The engine runs on a stream of its own; it is made
 to wait for torch's current stream before the call (the actions are ready) and torch's current stream for the engine's after it
@@ -27,7 +33,7 @@ from . import abi
 
 
 class VecEnv:
-    def __init__(self, eng, book=False):
+    def __init__(self, eng, book=False, history=0):
         self.eng = eng
         self.B, self.V = eng.B, eng.V
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -45,6 +51,18 @@ class VecEnv:
             self.own = torch.zeros((self.B, abi.VEC_OWN_WORDS), dtype=torch.float32, device=dev)
             self.time_ms = torch.zeros(self.B, dtype=torch.int64, device=dev)
             self.book_out = abi.VecBookOut(self.levels.data_ptr(), self.own.data_ptr(), self.time_ms.data_ptr())
+        self.history, self.hist_out = int(history), None
+        if self.history:
+            if not 1 <= self.history <= abi.MAX_HISTORY:
+                raise ValueError("VecEnv: history must be 0 or 1 .. %d" % abi.MAX_HISTORY)
+            K = self.history
+            self.hist_levels = torch.zeros((self.B, K, 4, eng.params.depth), dtype=torch.float32, device=dev)
+            self.hist_trades = torch.zeros((self.B, K, 2, eng.params.max_trades), dtype=torch.float32, device=dev)
+            self.hist_time_ms = torch.zeros((self.B, K), dtype=torch.int32, device=dev)
+            self.hist_valid = torch.zeros(self.B, dtype=torch.int32, device=dev)
+            self.hist_rec = torch.zeros(self.B, dtype=torch.int32, device=dev)
+            self.hist_out = abi.VecHistOut(self.hist_levels.data_ptr(), self.hist_trades.data_ptr(), self.hist_time_ms.data_ptr(),
+                                           self.hist_valid.data_ptr(), self.hist_rec.data_ptr())
         self.stream = torch.cuda.ExternalStream(eng.lob_stream(), device=dev)
         self.bad_actions = 0
         # (the zero fills above ran on torch's stream: the engine's first write must come after them)
@@ -56,6 +74,8 @@ class VecEnv:
         fn(*args, self.out)
         if self.book_out is not None:
             self.eng.vec_book(self.book_out)   # (right behind it on the engine's stream: the book as the step left it)
+        if self.hist_out is not None:
+            self.eng.vec_history(self.history, self.hist_out)
         cur.wait_stream(self.stream)      # what torch enqueues from here on sees the outputs
         return cur
 
