@@ -474,6 +474,45 @@ typedef struct lob_vec_hist_out {   /* all DEVICE pointers on the engine's GPU; 
 } lob_vec_hist_out;
 int lob_vec_history(lob_engine* e, int32_t K, const lob_vec_hist_out* out);
 
+/* ---- vector-env interface: save and restore the books on the device, by mask ---
+ * What a policy on the GPU needs to go BACK: branch rollouts from one state, rewind the books that broke a limit, compare two
+ * action sequences on common random numbers, restart the books that have finished while the others carry on.  Everything that
+ * depends on the event stream alone is in the market track, written once per episode and indexed by the book's event count; the
+ * agent-dependent state of a book is a few hundred bytes of struct-of-arrays words, and putting those back puts the book back --
+ * no pre-pass, no stream, no host.
+ *   A snapshot slot (0 <= slot < LOB_MAX_SNAPSHOTS) holds the environment state of all n_books books.  dev_mask: uint8 [n_books]
+ * in DEVICE memory on the engine's GPU, read in stream order; a nonzero byte selects the book, NULL selects every book.
+ *   ONE rule for restore.  A restored book continues exactly as it would have continued from the moment of the save: every later
+ * lob_vec_step, lob_step, lob_vec_observe, lob_get_books, lob_get_state, lob_get_reward, lob_get_terminal, lob_vec_book,
+ * lob_vec_history, lob_clear_inventory and lob_episode_stats gives, for that book, the bits it would have given then.  A book
+ * restored from terminal 1 or 2 to a saved state with terminal == 0 is live again.  A book outside the mask is not touched, not
+ * one byte of it.
+ *   What is saved: the book's environment state only -- its order, inventory, PnL, cursor and statistics words, the two rolling
+ * means of its own PnL (reward_measure LOB_REWARD_NORMED), the latest getState() and the environment's words of the step header
+ * (done, time, action, stepped, reward).  The market's windows belong to the episode's pre-pass and are not saved.  The learner is
+ * not touched: weights, traces, the two rl::State objects, the policy's random stream, TD errors and the memo tables stay as they
+ * are, and the cumulative counters of lob_get_counters are not wound back.
+ *   Learner calls after a restore: the learner's memory of the books' last transition then belongs to another trajectory, so
+ * lob_td_step, lob_td_step_begin, lob_eval_step and lob_handle_terminal return LOB_ESTATE (the message names the restore) from any
+ * successful lob_snapshot_restore until the next lob_reset.  The environment and vector-env calls go on working.
+ *   A snapshot belongs to the episode it was taken in: lob_reset invalidates every slot (track, days and stream may change there;
+ * the buffers stay allocated).  lob_snapshot_save with a NULL mask (re)starts the slot; with a mask it overwrites the selected
+ * books of a slot that already holds a full save of this episode, and is LOB_ESTATE if the slot holds none.
+ * lob_snapshot_restore of an empty or invalidated slot is LOB_ESTATE.
+ *   lob_snapshot_save / lob_snapshot_restore: one kernel enqueued on the engine's stream (lob_stream); the call returns at once --
+ * no host read, no copy, no synchronisation.  The only allocation is one hipMalloc the first time a slot is saved, kept until
+ * lob_snapshot_free / lob_destroy: THE FIRST SAVE OF A SLOT SYNCHRONISES THE DEVICE (hipMalloc does), every later call does not.
+ *   LOB_ESTATE also: before the first lob_reset; between lob_td_step_begin and lob_td_step_end; on an engine whose market track is
+ * a ring (a stream longer than LOB_TRACK_RING events: entries before the cursor have been overwritten, so an earlier event count
+ * cannot be served), for save and restore alike; on restore while the step log is enabled (its row rule total_ticks > n_rows +
+ * n_lost cannot survive total_ticks going back).  LOB_EINVAL: a NULL engine, or a slot outside [0, LOB_MAX_SNAPSHOTS).
+ * LOB_ENOMEM: the slot's buffer does not fit.  lob_snapshot_free releases the slot's buffer (after the work queued on the stream);
+ * of an empty slot it is LOB_OK.  A refused call changes nothing. */
+#define LOB_MAX_SNAPSHOTS 4
+int lob_snapshot_save(lob_engine* e, int32_t slot, const uint8_t* dev_mask);
+int lob_snapshot_restore(lob_engine* e, int32_t slot, const uint8_t* dev_mask);
+int lob_snapshot_free(lob_engine* e, int32_t slot);
+
 /* ---- episode statistics of the whole batch ---------------------------------
  * What the reference logs about ONE environment after an episode -- the `training_log` row of Runner::RunEpisode
  * (src/experiment/serial.cpp:81-88: getEpisodeReward, getEpisodePnL, total_ticks), Base::writeStats and getTotalTransactions

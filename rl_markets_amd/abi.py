@@ -164,6 +164,9 @@ class VecHistOut(C.Structure):
     _fields_ = [("levels", C.c_void_p), ("trades", C.c_void_p), ("time_ms", C.c_void_p), ("n_valid", C.c_void_p), ("rec", C.c_void_p)]
 
 
+# lob_snapshot_*: the snapshot slots of an engine (LOB_MAX_SNAPSHOTS)
+MAX_SNAPSHOTS = 4
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LOB_ENGINE_LIB: an experiment build of the same library (tools/exp_prof.py, tools/exp_variants.sh)
 LIB_PATH = os.environ.get("LOB_ENGINE_LIB") or os.path.join(_HERE, "csrc", "liblob_engine.so")
@@ -234,6 +237,9 @@ def load():
         "lob_vec_status": (C.c_int, [vp, P(C.c_int64)]),
         "lob_vec_book": (C.c_int, [vp, P(VecBookOut)]),
         "lob_vec_history": (C.c_int, [vp, C.c_int32, P(VecHistOut)]),
+        "lob_snapshot_save": (C.c_int, [vp, C.c_int32, C.c_void_p]),
+        "lob_snapshot_restore": (C.c_int, [vp, C.c_int32, C.c_void_p]),
+        "lob_snapshot_free": (C.c_int, [vp, C.c_int32]),
         "lob_td_step": (C.c_int, [vp, C.c_int32]),
         "lob_td_step_begin": (C.c_int, [vp]),
         "lob_td_split_supported": (C.c_int, [vp]),

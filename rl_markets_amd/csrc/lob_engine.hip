@@ -212,6 +212,15 @@ struct lob_engine {
     bool slog_armed = false;              // a lob_reset has come since lob_step_log_enable: the steps record
     lob_step_row* slog_stage = nullptr;   // lob_step_log_read's book-major staging buffer, grown like dump_dev
     size_t slog_stage_cap = 0;
+    // lob_snapshot_*: the slot buffers (one allocation each, made by the slot's first save), whether each holds a full save of the
+    // current episode, the descriptor table of the saved arrays (lob_launch.h SnapArgs; built with the first save) and the flag
+    // that keeps the learner calls off a restored batch until the next lob_reset
+    void* snap_buf[LOB_MAX_SNAPSHOTS] = {nullptr, nullptr, nullptr, nullptr};
+    bool snap_valid[LOB_MAX_SNAPSHOTS] = {false, false, false, false};
+    void* snap_tab = nullptr;
+    SnapArgs snap_args;
+    size_t snap_bytes = 0;
+    bool restored = false;
     bool have_events = false, was_reset = false;
     bool episode_open = false;  // a pre-pass ran and its window sums have not been rolled back to the stop point yet
     bool model_log = false;     // lob_model_log_enable: the step sums |delta| (td_stats_kernel)
@@ -798,6 +807,8 @@ void lob_destroy(lob_engine* e) {
     if (e->stats_dev) hipFree(e->stats_dev);
     step_log_free(e);
     if (e->slog_stage) hipFree(e->slog_stage);
+    for (void* p : e->snap_buf) if (p) hipFree(p);
+    if (e->snap_tab) hipFree(e->snap_tab);
     if (e->spx_gather) hipFree(e->spx_gather);
     if (e->spx_ev) hipEventDestroy(e->spx_ev);
     if (e->spx_total_host) hipHostFree(e->spx_total_host);
@@ -1335,6 +1346,8 @@ int lob_reset(lob_engine* e) {
     e->hint_step = 0;   // (the hand-back counts of the episode before say nothing about this one's first steps)
     e->rest_recent = 0;
     e->half_open = false;  // (a step begun before the reset -- e.g. an exchange that failed between the halves -- is abandoned with the episode)
+    for (bool& v : e->snap_valid) v = false;   // a snapshot belongs to the episode it was taken in (the buffers stay)
+    e->restored = false;
     return check_device_errors(e);
 }
 
@@ -1345,6 +1358,12 @@ static int need_reset(lob_engine* e, const char* who) {
 }
 // Between lob_td_step_begin and lob_td_step_end only the weight exchange may run (include/lob_engine.h): anything that moves
 // the books, the traces or the weights there would change what the second half consumes.
+// After a lob_snapshot_restore the learner's memory of the books' last transition (the rl::State objects, the traces, the hit lists)
+// belongs to another trajectory: the learner calls wait for the next lob_reset (include/lob_engine.h).
+static int not_restored(lob_engine* e, const char* who) {
+    if (e && e->restored) { lob_set_error(std::string(who) + ": books were put back by lob_snapshot_restore in this episode; the learner runs again after the next lob_reset"); return LOB_ESTATE; }
+    return LOB_OK;
+}
 static int not_mid_step(lob_engine* e, const char* who) {
     if (e && e->half_open) { lob_set_error(std::string(who) + ": a learner step is half done (lob_td_step_begin without lob_td_step_end)"); return LOB_ESTATE; }
     return LOB_OK;
@@ -1511,6 +1530,110 @@ int lob_vec_history(lob_engine* e, int32_t K, const lob_vec_hist_out* out) {
         lobk_vec_history(e->stream, s, K, *out);
     }
     HIPCHK(hipGetLastError());
+    return LOB_OK;
+}
+
+// ---- book snapshots (include/lob_engine.h lob_snapshot_*; lob_tu_snapshot.hip) ----
+// The descriptor table of the arrays a snapshot holds and their places in a slot buffer, built once per engine with the first save:
+// every array of LOB_ENV_FIELDS, the rolling means pnl_ups / pnl_downs, then the per-book records (LHdr's five environment words,
+// slot 2 of vars).  Arrays at multiples of 16 bytes, in the live layout.
+static int snap_prepare(lob_engine* e) {
+    if (e->snap_tab) return LOB_OK;
+    const size_t B = (size_t)e->B;
+    std::vector<SnapRow> r4, r8;
+    std::vector<SnapArr> arrs;
+    size_t off = 0, max_bytes = 0;
+    auto add = [&](void* live, size_t width, size_t rows) {
+        const size_t bytes = rows * B * width;
+        arrs.push_back(SnapArr{live, (u64)off, (u64)bytes, 0});
+        for (size_t r = 0; r < rows; r++) (width == 4 ? r4 : r8).push_back(SnapRow{(char*)live + r * B * width, (u64)(off + r * B * width)});
+        max_bytes = std::max(max_bytes, bytes);
+        off = (off + bytes + 15) & ~(size_t)15;
+    };
+#define X(t, n) static_assert(sizeof(t) == 4 || sizeof(t) == 8, "two element widths"); add(e->S.n.p, sizeof(t), 1);
+    LOB_ENV_FIELDS(X)
+#undef X
+    for (const RMPtrs* m : {&e->S.pnl_ups, &e->S.pnl_downs}) {
+        add(m->ring.p, 8, (size_t)m->w); add(m->cnt.p, 4, 1); add(m->head.p, 4, 1); add(m->sum.p, 8, 1); add(m->mean.p, 8, 1); add(m->s.p, 8, 1);
+    }
+    SnapArgs& a = e->snap_args;
+    a.off_hdr = off; off = (off + 4 * B * 4 + 15) & ~(size_t)15;
+    a.off_reward = off; off = (off + B * 8 + 15) & ~(size_t)15;
+    a.off_vars = off; off += B * 64;
+    a.n4 = (i32)r4.size(); a.n8 = (i32)r8.size(); a.n_arr = (i32)arrs.size(); a.B = e->B;
+    a.max_bytes = max_bytes;
+    a.hdr = e->S.hdr.p; a.vars = e->S.vars.p;
+    r4.insert(r4.end(), r8.begin(), r8.end());
+    const size_t rows_bytes = r4.size() * sizeof(SnapRow), arrs_bytes = arrs.size() * sizeof(SnapArr);
+    void* tab = nullptr;
+    if (hipMalloc(&tab, rows_bytes + arrs_bytes) != hipSuccess) { (void)hipGetLastError(); lob_set_error("lob_snapshot_save: no room for the descriptor table"); return LOB_ENOMEM; }
+    if (hipMemcpy(tab, r4.data(), rows_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy((char*)tab + rows_bytes, arrs.data(), arrs_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        hipFree(tab);
+        lob_set_error("lob_snapshot_save: descriptor table upload failed");
+        return LOB_EHIP;
+    }
+    a.rows = (const SnapRow*)tab;
+    a.arrs = (const SnapArr*)((char*)tab + rows_bytes);
+    e->snap_tab = tab;
+    e->snap_bytes = off;
+    return LOB_OK;
+}
+static int snap_entry(lob_engine* e, int32_t slot, const char* who) {
+    if (!e) { lob_set_error(std::string(who) + ": NULL engine"); return LOB_EINVAL; }
+    if (slot < 0 || slot >= LOB_MAX_SNAPSHOTS) { lob_set_error(std::string(who) + ": slot " + std::to_string(slot) + " is outside [0, " + std::to_string(LOB_MAX_SNAPSHOTS) + ")"); return LOB_EINVAL; }
+    int rc = need_reset(e, who);
+    if (rc) return rc;
+    if ((rc = not_mid_step(e, who))) return rc;
+    if (e->chunked) { lob_set_error(std::string(who) + ": the market track of this stream is a ring (longer than LOB_TRACK_RING events): entries before the cursor are gone, no earlier state can be served"); return LOB_ESTATE; }
+    return LOB_OK;
+}
+int lob_snapshot_save(lob_engine* e, int32_t slot, const uint8_t* dev_mask) {
+    int rc = snap_entry(e, slot, "lob_snapshot_save");
+    if (rc) return rc;
+    if (dev_mask && !e->snap_valid[slot]) { lob_set_error("lob_snapshot_save: a masked save needs a slot that holds a full save (NULL mask) of this episode"); return LOB_ESTATE; }
+    HIPCHK(hipSetDevice(e->device));
+    if ((rc = snap_prepare(e))) return rc;
+    if (!e->snap_buf[slot]) {   // (the slot's one allocation: hipMalloc synchronises the device)
+        if (hipMalloc(&e->snap_buf[slot], e->snap_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            e->snap_buf[slot] = nullptr;
+            lob_set_error("lob_snapshot_save: no room for the slot's buffer (" + std::to_string(e->snap_bytes) + " bytes)");
+            return LOB_ENOMEM;
+        }
+    }
+    {
+        TimedLaunch t(e, dev_mask ? "snapshot_masked_kernel" : "snapshot_all_kernel", nullptr, true);
+        lobk_snapshot(e->stream, false, e->snap_args, e->snap_buf[slot], dev_mask);
+    }
+    HIPCHK(hipGetLastError());
+    e->snap_valid[slot] = true;
+    return LOB_OK;
+}
+int lob_snapshot_restore(lob_engine* e, int32_t slot, const uint8_t* dev_mask) {
+    int rc = snap_entry(e, slot, "lob_snapshot_restore");
+    if (rc) return rc;
+    if (e->slog_n) { lob_set_error("lob_snapshot_restore: the step log is enabled (a row is due where total_ticks > n_rows + n_lost: total_ticks cannot go back under it)"); return LOB_ESTATE; }
+    if (!e->snap_valid[slot] || !e->snap_buf[slot]) { lob_set_error("lob_snapshot_restore: slot " + std::to_string(slot) + " holds no save of this episode"); return LOB_ESTATE; }
+    HIPCHK(hipSetDevice(e->device));
+    {
+        TimedLaunch t(e, dev_mask ? "snapshot_masked_kernel" : "snapshot_all_kernel", nullptr, true);
+        lobk_snapshot(e->stream, true, e->snap_args, e->snap_buf[slot], dev_mask);
+    }
+    HIPCHK(hipGetLastError());
+    e->restored = true;
+    e->hits_ok = false;
+    return LOB_OK;
+}
+int lob_snapshot_free(lob_engine* e, int32_t slot) {
+    if (!e) { lob_set_error("lob_snapshot_free: NULL engine"); return LOB_EINVAL; }
+    if (slot < 0 || slot >= LOB_MAX_SNAPSHOTS) { lob_set_error("lob_snapshot_free: slot " + std::to_string(slot) + " is outside [0, " + std::to_string(LOB_MAX_SNAPSHOTS) + ")"); return LOB_EINVAL; }
+    if (!e->snap_buf[slot]) return LOB_OK;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));   // (a save or restore still queued uses the buffer)
+    hipFree(e->snap_buf[slot]);
+    e->snap_buf[slot] = nullptr;
+    e->snap_valid[slot] = false;
     return LOB_OK;
 }
 
@@ -2034,12 +2157,14 @@ int lob_td_step(lob_engine* e, int32_t n_steps) {
     if (rc) return rc;
     if (n_steps < 0) return LOB_EINVAL;
     if (e->half_open) { lob_set_error("lob_td_step: a step is half done (lob_td_step_begin without lob_td_step_end)"); return LOB_ESTATE; }
+    if ((rc = not_restored(e, "lob_td_step"))) return rc;
     return run_steps(e, n_steps, 0);
 }
 int lob_td_step_begin(lob_engine* e) {
     int rc = need_reset(e, "lob_td_step_begin");
     if (rc) return rc;
     if (e->half_open) { lob_set_error("lob_td_step_begin: the previous step has not been ended"); return LOB_ESTATE; }
+    if ((rc = not_restored(e, "lob_td_step_begin"))) return rc;
     if (e->plan.groups > 1) { lob_set_error("lob_td_step_begin: not with two book groups (LOB_GROUPS=2)"); return LOB_ESTATE; }
     return run_steps(e, 1, 0, 1);
 }
@@ -2055,6 +2180,7 @@ int lob_eval_step(lob_engine* e, int32_t n_steps) {
     if (rc) return rc;
     if (n_steps < 0) return LOB_EINVAL;
     if (e->half_open) { lob_set_error("lob_eval_step: a learner step is half done"); return LOB_ESTATE; }
+    if ((rc = not_restored(e, "lob_eval_step"))) return rc;
     return run_steps(e, n_steps, 1);
 }
 
@@ -2171,6 +2297,7 @@ int lob_step_log_read(lob_engine* e, int32_t first_sel, int32_t n_sel, int32_t f
 int lob_handle_terminal(lob_engine* e) {
     if (!e) return LOB_EINVAL;
     { int rc = not_mid_step(e, "lob_handle_terminal"); if (rc) return rc; }
+    { int rc = not_restored(e, "lob_handle_terminal"); if (rc) return rc; }
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(clear_traces_kernel, dim3(grid_lanes(e->B)), dim3(256), 0, e->stream, e->S);
     HIPCHK(hipGetLastError());

@@ -1,6 +1,6 @@
-// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is nine
+// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is ten
 // .hip files built in parallel: lob_engine.hip -- the C ABI's host side and the update / memo / trace kernels --, lob_tu_env.hip,
-// lob_tu_prepass.hip, lob_tu_learn.hip, lob_tu_stats.hip, lob_tu_steplog.hip, lob_tu_vec.hip, lob_tu_vecbook.hip, lob_tu_vechist.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
+// lob_tu_prepass.hip, lob_tu_learn.hip, lob_tu_stats.hip, lob_tu_steplog.hip, lob_tu_vec.hip, lob_tu_vecbook.hip, lob_tu_vechist.hip, lob_tu_snapshot.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
 // lob_engine.hip used when it held the launches itself.  Kernels measured and lost (NOTES.md "Round 4") are only compiled with
 // -DLOB_EXPERIMENTS (tools/exp_variants.sh); a product build answers LOB_EXPERIMENTS-only requests with the product kernel.
 #ifndef LOB_LAUNCH_H
@@ -140,6 +140,34 @@ struct VecHistSrc {
     i32 w_ask_px, w_ask_vol, w_bid_px, w_bid_vol, w_trades;
 };
 void lobk_vec_history(hipStream_t st, const VecHistSrc& s, int K, const lob_vec_hist_out& out);
+
+// ---- lob_tu_snapshot.hip ----
+// What lob_snapshot_save / lob_snapshot_restore (include/lob_engine.h) move, as a descriptor table in device memory (the DevState does
+// not grow, and sixty pointers do not travel by value): one SnapRow per [B] row of every saved array -- the arrays of LOB_ENV_FIELDS,
+// the rolling means pnl_ups / pnl_downs (a ring of w rows: w entries) --, the `n4` rows of 4-byte elements first, the `n8` rows of
+// 8-byte elements behind them (the masked path: a lane per book walks the rows); one SnapArr per whole array (the all-books path:
+// contiguous bytes on both sides).  `off`: the array's (row's) place in a slot buffer, arrays at multiples of 16 bytes in the live
+// layout.  The two per-book records -- the environment's words of LHdr, slot 2 of `vars` -- come as kernel arguments.
+#define LOB_SNAP_BLOCK 256
+struct SnapRow {
+    void* live;   // the row's first element in the engine's state
+    u64 off;      // ... and its byte offset in a slot buffer
+};
+struct SnapArr {
+    void* live;
+    u64 off, bytes, _pad;
+};
+struct SnapArgs {
+    const SnapRow* rows;   // [n4 + n8], device memory
+    const SnapArr* arrs;   // [n_arr], device memory
+    i32 n4, n8, n_arr, B;
+    u64 max_bytes;         // the largest array
+    LHdr* hdr;             // [B]: done, time_ms, action, stepped, reward are the environment's
+    f32* vars;             // [B][3][16]: slot 2
+    u64 off_hdr, off_reward, off_vars;   // slot buffer: i32 [4][B] (done, time_ms, action, stepped), f64 [B], f32 [B][16]
+};
+// snapshot_masked_kernel (dev_mask: uint8 [B] in device memory, nonzero selects) or, dev_mask == NULL, snapshot_all_kernel
+void lobk_snapshot(hipStream_t st, bool restore, const SnapArgs& a, void* slot, const uint8_t* dev_mask);
 
 // ---- lob_tu_learn.hip ----
 // learn_q_pair_kernel / learn_q_lane_kernel<algo, vt, tr>: vt = 8 when the state has eight variables (else 0)

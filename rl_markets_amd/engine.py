@@ -302,6 +302,21 @@ class Engine:
         enqueued on the engine's stream."""
         self._check(self.lib.lob_vec_history(self.h, int(K), C.byref(out)))
 
+    def snapshot_save(self, slot, mask_ptr=None):
+        """lob_snapshot_save: the environment state of the books selected by the DEVICE mask at address `mask_ptr` (uint8 [B],
+        nonzero selects; None: every book, which (re)starts the slot) into snapshot slot `slot` (0 .. abi.MAX_SNAPSHOTS - 1);
+        enqueued on the engine's stream.  The first save of a slot allocates its buffer."""
+        self._check(self.lib.lob_snapshot_save(self.h, int(slot), mask_ptr))
+
+    def snapshot_restore(self, slot, mask_ptr=None):
+        """lob_snapshot_restore: the selected books continue exactly as they would have from the moment of the save; the others
+        are not touched.  Enqueued on the engine's stream.  The learner calls are refused from here to the next reset()."""
+        self._check(self.lib.lob_snapshot_restore(self.h, int(slot), mask_ptr))
+
+    def snapshot_free(self, slot):
+        """lob_snapshot_free: release the slot's buffer (an empty slot is fine)."""
+        self._check(self.lib.lob_snapshot_free(self.h, int(slot)))
+
     def lob_stream(self):
         """lob_stream: the engine's hipStream_t as an integer."""
         return int(self.lib.lob_stream(self.h) or 0)

@@ -21,6 +21,18 @@ VecEnv(eng, history=K) keeps the last K event records of every book on the devic
 book's stream; .hist_valid i32 [B] counts the slots that hold a record and .hist_rec i32 [B] is the index of the newest one within
 the book's stream (-1: none).  Refreshed like the book tensors; the two options are independent.
 
+save(slot, mask) / restore(slot, mask) keep and put back the books' environment state on the device (lob_snapshot_save /
+lob_snapshot_restore, 0 <= slot < abi.MAX_SNAPSHOTS): mask is a torch.bool or torch.uint8 tensor [B] on the engine's device (nonzero
+selects the book), None every book.  A restored book continues exactly as it would have from the moment of the save; restore()
+returns the refreshed `obs` (and refreshes the book / history tensors).  Per-book restarts on the same day:
+
+    obs = env.reset(); env.save(0)                 # the state right after the reset
+    ...
+    obs = env.restore(0, mask=env.terminal != 0)   # the books that are over play their day again, the others carry on
+
+A snapshot belongs to its episode (reset() voids it), and after a restore the engine's own learner calls (td_step, eval_step) are
+refused until the next reset().  A VecEnv that never calls save() / restore() launches and allocates nothing for them.
+
 step() reads the actions from the tensor's device memory and writes into five persistent tensors (lob_vec_step,
 include/lob_engine.h): no copy to or from the host and no synchronisation.  The engine runs on a stream of its own; it is made
 to wait for torch's current stream before the call (the actions are ready) and torch's current stream for the engine's after it
@@ -100,6 +112,38 @@ class VecEnv:
         # record an event on when the tensor is freed -- possibly after Engine.close() has destroyed that stream.
         actions.record_stream(cur)
         return self.obs, self.reward, self.terminal, self.stepped
+
+    def _mask_ptr(self, mask, who):
+        if mask is None:
+            return None
+        if (not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool) or not mask.is_cuda or mask.device != self.device
+                or mask.shape != (self.B,) or not mask.is_contiguous()):
+            raise ValueError("VecEnv.%s: mask must be a contiguous uint8 or bool CUDA tensor of shape (%d,) on the engine's device" % (who, self.B))
+        return mask.data_ptr()
+
+    def save(self, slot=0, mask=None):
+        """lob_snapshot_save: the environment state of the selected books (mask None: all, which (re)starts the slot) into `slot`.
+        The slot's first save allocates its buffer and with that synchronises the device; later ones only enqueue."""
+        ptr = self._mask_ptr(mask, "save")
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)      # the mask is ready
+        self.eng.snapshot_save(slot, ptr)
+        cur.wait_stream(self.stream)
+        if mask is not None:
+            mask.record_stream(cur)       # (as step() does with the actions)
+
+    def _restore_observe(self, slot, ptr, out):
+        self.eng.snapshot_restore(slot, ptr)
+        self.eng.vec_observe(out)
+
+    def restore(self, slot=0, mask=None):
+        """lob_snapshot_restore of the selected books from `slot`, then the observation (and the book / history tensors) of the
+        batch as it now stands.  Returns obs."""
+        ptr = self._mask_ptr(mask, "restore")
+        cur = self._call(self._restore_observe, slot, ptr)
+        if mask is not None:
+            mask.record_stream(cur)
+        return self.obs
 
     def status(self):
         """lob_vec_status: waits once; LOB_OK, or LOB_EINVAL when actions were out of range since the last call (their number
