@@ -126,10 +126,54 @@ struct EnvCtx {
             for (int i = 0; i < 12; i++) prow_[20 + i] += acc_[i];
         }
     }
+    // The event loop's passes as the WAVE runs them (tools/exp_envpass.py): every lane counts the passes it takes and times them by
+    // how many lanes were still in the loop; the lane that stayed longest has seen all of the wave's passes and writes them, to its own
+    // book's row (lob_debug_prof sums the rows).  Slots: [32] wave-steps, [33] passes, [33 + n] wave-steps of n passes (n = 24: or more),
+    // [58 + i] passes with 64-33 / 32-17 / 16-9 / 8-5 / 4-2 / 1 lanes left, [64 + i] their clocks from the loop top to the requests
+    // (phase 23), [70 + i] their clocks in the pass (phase 24), [76] passes that took the general path.
+    mutable int pp_n_ = 0, pp_bin_ = 0, pp_gen_ = 0;
+    mutable long long pp_t_ = 0;
+    mutable long long pp_cnt_[6] = {0, 0, 0, 0, 0, 0}, pp_c23_[6] = {0, 0, 0, 0, 0, 0}, pp_c24_[6] = {0, 0, 0, 0, 0, 0};
+    __device__ void pass_top() const {
+        const int n = __popcll(__ballot(1));
+        pp_bin_ = n > 32 ? 0 : n > 16 ? 1 : n > 8 ? 2 : n > 4 ? 3 : n > 1 ? 4 : 5;
+        pp_t_ = clock64();
+    }
+    __device__ void pass_mid() const {
+        const long long now = clock64();
+#pragma unroll
+        for (int i = 0; i < 6; i++) pp_c23_[i] += pp_bin_ == i ? now - pp_t_ : 0;
+        pp_t_ = now;
+    }
+    __device__ void pass_end(bool fast) const {
+        const long long now = clock64();
+#pragma unroll
+        for (int i = 0; i < 6; i++) { pp_c24_[i] += (fast && pp_bin_ == i) ? now - pp_t_ : 0; pp_cnt_[i] += (fast && pp_bin_ == i) ? 1 : 0; }
+        pp_gen_ += fast ? 0 : 1;
+        pp_n_++;
+    }
+    __device__ void pass_flush() const {  // (behind the loop: the wave's lanes that stepped are together again)
+        int mx = 0;
+#pragma unroll
+        for (int bit = 32; bit; bit >>= 1) mx += __any(pp_n_ >= mx + bit) ? bit : 0;
+        const unsigned long long who = __ballot(pp_n_ == mx);
+        if (!S.prof || who == 0 || (int)(threadIdx.x & 63) != __builtin_ctzll(who)) return;
+        i64* row = S.prof + (size_t)b * LOB_PROF_N;
+        row[32] += 1;
+        row[33] += mx;
+        row[33 + (mx < 24 ? (mx > 0 ? mx : 1) : 24)] += 1;
+#pragma unroll
+        for (int i = 0; i < 6; i++) { row[58 + i] += pp_cnt_[i]; row[64 + i] += pp_c23_[i]; row[70 + i] += pp_c24_[i]; }
+        row[76] += pp_gen_;
+    }
 #else
     __device__ void prof_start(i64*, int, long long = 0) const {}
     __device__ void mark(int) const {}
     __device__ void flush() const {}
+    __device__ void pass_top() const {}
+    __device__ void pass_mid() const {}
+    __device__ void pass_end(bool) const {}
+    __device__ void pass_flush() const {}
 #endif
     __device__ EnvCtx(const DevParams& p, const DevState& s, int book, const TickLds* t) : P(p), S(s), b(book), tk(t) {
         const size_t first = s.rec_phase ? (size_t)s.rec_phase[book] : (size_t)book * (size_t)s.n_events;
@@ -579,10 +623,10 @@ __device__ inline i64 rowlev_volume(const EnvCtx& c, const RowLev& R, int side, 
     return m ? (i64)(i32)v : 0;
 }
 __device__ inline i64 full_volume(const EnvCtx& c, const RowLev& R, int side, f64 price) { return rowlev_volume(c, R, side, key4(price)); }
-__device__ inline void row_volumes_k(const EnvCtx& c, bool a_on, bool b_on, f64 ka, f64 kb, const RowLev& L, i64& a_v, i64& b_v) {
-    const i64 va = rowlev_volume(c, L, 0, ka), vb = rowlev_volume(c, L, 1, kb);
-    a_v = a_on ? va : 0;
-    b_v = b_on ? vb : 0;
+// volume resting at ONE side's order key in a row (pass_fast scans a side only while some lane's order on it is on)
+__device__ inline i64 row_volume_side(const EnvCtx& c, int side, bool on, f64 k, const RowLev& L) {
+    const i64 v = rowlev_volume(c, L, side, k);
+    return on ? v : 0;
 }
 #endif
 
@@ -1232,6 +1276,16 @@ __device__ inline bool perform_action(const EnvCtx& c, EnvR& e, int action, Trac
 #define LOB_ENV_PASS_FIELDS(X) \
     X(k) X(time_ms) X(rec_cur) X(rec_last) X(pf) X(mid) X(mid_prev) X(position) X(lo_vol_step) X(pnl_step) X(momentum_pnl_step) \
     X(ep_pnl) X(events) X(a_ntr) X(a_on) X(a_oqh) X(a_oqt) X(a_oex) X(b_ntr) X(b_on) X(b_oqh) X(b_oqt) X(b_oex)
+// -DLOB_PASS_SKIPS=0: the pass without its wave-uniform skips (every block in select form for every lane, as up to round 6), for
+// A/B builds and the pass profile (tools/exp_envpass.py); the results are the same either way.
+#ifndef LOB_PASS_SKIPS
+#define LOB_PASS_SKIPS 1
+#endif
+#if LOB_PASS_SKIPS
+#define LOB_PASS_ANY(p) __any(p)   // over the lanes still in the event loop
+#else
+#define LOB_PASS_ANY(p) true
+#endif
 struct FastKeys {
     f64 ka, kb;  // key4 of the two order prices
 };
@@ -1277,31 +1331,31 @@ __device__ inline void update_order_sel(i32& on, i64 size, i64& qh, i64& qt, i64
     qh = gone ? 0 : nh;
     qt = gone ? 0 : nt;
 }
-// volume resting at the two order keys in one row
-__device__ inline void row_volumes_k(const EnvCtx& c, bool a_on, bool b_on, f64 ka, f64 kb, const RowFull& L, i64& a_v, i64& b_v) {
+// volume resting at ONE side's order key in one row (pass_fast scans a side only while some lane's order on it is on)
+__device__ inline i64 row_volume_side(const EnvCtx& c, int side, bool on, f64 k, const RowFull& L) {
     const int D = c.P.D;
-    uint32_t va = 0, vb = 0;
-    bool fa = false, fb = false;
+    const uint32_t* px = side == 0 ? L.apx : L.bpx;
+    const uint32_t* vol = side == 0 ? L.avol : L.bvol;
+    uint32_t v = 0;
+    bool f = false;
 #pragma unroll
     for (int l = 0; l < LOB_MAX_DEPTH; l++) {
-        const f32 pa = l < D ? __uint_as_float(L.apx[l]) : 0.0f;
-        const f32 pb = l < D ? __uint_as_float(L.bpx[l]) : 0.0f;
-        const bool ha = pa != 0.0f && key4((f64)pa) == ka;  // price keys are unique per side (lob_validate_stream)
-        const bool hb = pb != 0.0f && key4((f64)pb) == kb;
-        va = ha ? L.avol[l] : va; fa = fa || ha;
-        vb = hb ? L.bvol[l] : vb; fb = fb || hb;
+        const f32 p = l < D ? __uint_as_float(px[l]) : 0.0f;
+        const bool hit = p != 0.0f && key4((f64)p) == k;  // price keys are unique per side (lob_validate_stream)
+        v = hit ? vol[l] : v; f = f || hit;
     }
-    a_v = (a_on && fa) ? (i64)(i32)va : 0;
-    b_v = (b_on && fb) ? (i64)(i32)vb : 0;
+    return (on && f) ? (i64)(i32)v : 0;
 }
 // one pass: 0 = another event follows, 1 = the step is complete.  `L` = the level arrays of row t.rec_first.
+// Blocks that are, by their own select form, a no-op for a lane without a trade / without that side's order / without a crossed
+// order are skipped when NO lane still in the loop has one (LOB_PASS_ANY: two passes in three are run for 16 books or fewer, one in five for a single one -- profiles/r07_env_pass.txt).
 template <class TH, class ROW>  // TrackHead64, or the whole Track entry; RowFull, or RowLev (levels across 16 lanes)
 __device__ inline int pass_fast(const EnvCtx& c, EnvR& h, StepAgg& g, const TH& t, ROW& L, const FastKeys& K, const f64* spread_mean = nullptr) {
     const DevParams& P = c.P;
     h.pnl_step = 0.0;
     const f64 tp0 = (f64)t.tr_px[0], tp1 = (f64)t.tr_px[1];
     const i64 tv0 = (t.info & 3) > 0 ? t.tr_vol[0] : 0, tv1 = (t.info & 3) > 1 ? t.tr_vol[1] : 0;
-    const f64 tk0 = key4(tp0), tk1 = key4(tp1);
+    f64 tk0 = 0.0, tk1 = 0.0;  // (read only beside tv0 > 0 / tv1 > 0: update_order_sel)
     h.pf = t.rec_first;
     const f64 mp = h.mid;
     i64 au_vol = 0; f64 au_proxy = 0.0, au_value = 0.0;
@@ -1332,8 +1386,11 @@ __device__ inline int pass_fast(const EnvCtx& c, EnvR& h, StepAgg& g, const TH& 
         h.b_on = done ? 0 : h.b_on;                                                                         \
         h.b_ntr += done ? 1 : 0;                                                                            \
     }
-    LOB_FP_ASK(tp0, tv0) LOB_FP_ASK(tp1, tv1)   // ascending prices
-    LOB_FP_BID(tp1, tv1) LOB_FP_BID(tp0, tv0)   // descending
+    if (LOB_PASS_ANY(tv0 > 0 || tv1 > 0)) {
+        tk0 = key4(tp0); tk1 = key4(tp1);
+        LOB_FP_ASK(tp0, tv0) LOB_FP_ASK(tp1, tv1)   // ascending prices
+        LOB_FP_BID(tp1, tv1) LOB_FP_BID(tp0, tv0)   // descending
+    }
 #undef LOB_FP_ASK
 #undef LOB_FP_BID
     // UpdateBookProfiles: StashState, then ApplyChanges (-> UpdateOrder) for every applied row
@@ -1341,10 +1398,15 @@ __device__ inline int pass_fast(const EnvCtx& c, EnvR& h, StepAgg& g, const TH& 
     const i64 a_lv = g.cv_a, b_lv = g.cv_b;
     for (int r = t.rec_first; r <= t.rec_last; r++) {
         if (r != t.rec_first) row_full_load(c, r, L);
-        i64 a_v, b_v;
-        row_volumes_k(c, h.a_on != 0, h.b_on != 0, K.ka, K.kb, L, a_v, b_v);
-        update_order_sel(h.a_on, h.a_osz, h.a_oqh, h.a_oqt, h.a_oex, K.ka, a_lv, a_v, tk0, tk1, tv0, tv1);
-        update_order_sel(h.b_on, h.b_osz, h.b_oqh, h.b_oqt, h.b_oex, K.kb, b_lv, b_v, tk0, tk1, tv0, tv1);
+        i64 a_v = 0, b_v = 0;  // (a side whose order is off reads 0, and UpdateOrder leaves it alone)
+        if (LOB_PASS_ANY(h.a_on != 0)) {
+            a_v = row_volume_side(c, 0, h.a_on != 0, K.ka, L);
+            update_order_sel(h.a_on, h.a_osz, h.a_oqh, h.a_oqt, h.a_oex, K.ka, a_lv, a_v, tk0, tk1, tv0, tv1);
+        }
+        if (LOB_PASS_ANY(h.b_on != 0)) {
+            b_v = row_volume_side(c, 1, h.b_on != 0, K.kb, L);
+            update_order_sel(h.b_on, h.b_osz, h.b_oqh, h.b_oqt, h.b_oex, K.kb, b_lv, b_v, tk0, tk1, tv0, tv1);
+        }
         g.cv_a = a_v;
         g.cv_b = b_v;
     }
@@ -1357,8 +1419,9 @@ __device__ inline int pass_fast(const EnvCtx& c, EnvR& h, StepAgg& g, const TH& 
     h.k++;
     // BookUtils::HandleAdverseSelection (book.cpp:551-592) against the touch of the new snapshot
     i64 ad_vol = 0; f64 ad_proxy = 0.0, ad_value = 0.0;
-    {
-        const f64 bap = (f64)t.bap, bbp = (f64)t.bbp, rp = h.mid_prev;
+    const f64 bap = (f64)t.bap, bbp = (f64)t.bbp;
+    if (LOB_PASS_ANY((h.a_on && h.a_opx <= bbp) || (h.b_on && h.b_opx >= bap))) {
+        const f64 rp = h.mid_prev;
         const bool ha = h.a_on && h.a_opx <= bbp;
         {
             const i64 rem = h.a_osz - h.a_oex > 0 ? h.a_osz - h.a_oex : 0;
@@ -1410,6 +1473,7 @@ __device__ inline int event_loop_fast(const EnvCtx& c, EnvR& e, StepAgg& g, TE& 
         // the next event's entry and first row are requested a pass ahead (wasted on a step's last pass: skipping them there on a
         // "step ends here" bit computed by the pre-pass measured SLOWER, 0.104 vs 0.098 ms -- the conditional requests split the
         // batch of loads)
+        c.pass_top();
         const TE tn = *reinterpret_cast<const TE*>(&c.track(h.k + 1));
         // the fast pass needs: the event inside the track, freshly placed orders behind it, its trade list whole, and the row
         // it was handed (a step's first row is the record after the current snapshot -- anything else is reloaded)
@@ -1420,6 +1484,7 @@ __device__ inline int event_loop_fast(const EnvCtx& c, EnvR& e, StepAgg& g, TE& 
             ROW Ln = L;  // next pass's first row, in flight during this one
             { const int rn = t.rec_last + 1; row_full_load(c, rn < last_row ? rn : last_row, Ln); }
             c.mark(23);  // loop top: next entry / next row requested
+            c.pass_mid();
             st = pass_fast(c, h, g, t, L, K, sizeof(TE) == sizeof(Track) ? &reinterpret_cast<const Track*>(&t)->spread_mean : nullptr);
             L = Ln;
             have_next_row = true;
@@ -1434,11 +1499,13 @@ __device__ inline int event_loop_fast(const EnvCtx& c, EnvR& e, StepAgg& g, TE& 
             st = step_event<2>(c, e, g, t32);
             h = e;
         }
+        c.pass_end(have_next_row);
         if (st != 0) break;
         if (!have_next_row) row_full_load(c, h.rec_cur + 1 < last_row ? h.rec_cur + 1 : last_row, L);
         t = tn;
     }
     c.mark(25);  // waiting for the wave's slowest lane
+    c.pass_flush();
 #define X(n) e.n = h.n;
     LOB_ENV_PASS_FIELDS(X)
 #undef X

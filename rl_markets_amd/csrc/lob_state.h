@@ -197,7 +197,7 @@ struct __attribute__((aligned(64))) LHdr {
 #define LOB_ML_BLOCKS 256
 #define LOB_ML_ROWS 8192
 #define LOB_PERSIST_N 32
-#define LOB_PROF_N 32
+#define LOB_PROF_N 80   // [0, 32): phase clocks; [32, 80): the env step's event passes (lob_env.h EnvCtx::pass_flush)
 #define LOB_MK_REC 10         /* doubles per memo record: S0 of the nine actions + the theta version it was computed under */
 #define LOB_MK_PROBES 16
 #define LOB_HL_CAP 23         /* additions of a hit list that the kernels keep in registers / LDS rows (the mean is 8, the 99th percentile 17, once

@@ -30,7 +30,7 @@ B = 65536
 eng = engine.Engine(p, B); eng.gen_events(g); eng.reset()
 eng.td_step(60); eng.sync()
 eng.lib.lob_debug_prof.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]
-out = (ctypes.c_int64 * 32)()
+out = (ctypes.c_int64 * 80)()   # LOB_PROF_N (the env step's pass counters behind the 32 phase clocks: tools/exp_envpass.py)
 assert eng.lib.lob_debug_prof(eng.h, out) == 0
 a = list(out)
 N = 100
