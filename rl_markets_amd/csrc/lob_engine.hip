@@ -683,6 +683,8 @@ int lob_create(const lob_params* p, int32_t n_books, int32_t device, lob_engine*
         P.cwords4 = (int)((cwords + 3) / 4);
         alloc(&S.theta_nzx, P.memo ? (size_t)P.M / 32 + 1 : 1); alloc(&S.theta_nzc, (size_t)P.cwords4 * 4);
         if (P.memo) alloc(&S.theta_nzd, 2 * ((size_t)P.M / 32 + 1));
+        // (the per-sum action masks behind it: for the pair kernel only -- 80 MB at M = 20 M)
+        if (P.memo && e->plan.q_lanes && e->plan.q_pair) alloc(&S.theta_nzm, 2 * fold_mask_words((uint32_t)P.M));
         alloc(&S.slow_list, 2 * B); alloc(&S.slow_n, 4); alloc(&S.hl_rec, P.memo ? (size_t)LOB_HL_REC * B : 1); alloc(&S.hl_dirty, 1);
         if (rc == LOB_OK && hipMemsetAsync(S.hl_rec, 0xff, (P.memo ? (size_t)LOB_HL_REC * B : 1) * 8, e->stream) != hipSuccess) rc = LOB_EHIP;
         if (rc == LOB_OK && hipMemsetAsync(S.hl_dirty, 0xff, 4, e->stream) != hipSuccess) rc = LOB_EHIP;
@@ -1991,6 +1993,7 @@ static int learn_half(lob_engine* e, const StepPlan& sp, const StepGroup& gr) {
         TimedLaunch t(e, "learn_kernel", st);
         if (pl.q_lanes) {
             const bool pair = pl.q_pair;
+            if (pair && !e->S.theta_nzm) { lob_set_error("learn_q_pair_kernel: no action-mask table (theta_nzm)"); return LOB_ESTATE; }
             const int gq = pair ? std::min(LOB_QP_OCC * e->n_cus, (nb + LOB_QP_BOOKS - 1) / LOB_QP_BOOKS) : std::min(e->n_cus, (nb + LOB_QL_BLOCK - 1) / LOB_QL_BLOCK);
             const size_t lds = pair ? qpair_lds_bytes(e->P.cwords4) : qlane_lds_bytes(e->P.cwords4);
             lobk_learn_q(st, pair, algo, e->P.V == 8, pl.fuse, gq, lds, (const DevParams*)e->P_dev, e->S, rnd, lpar, sp.ver, sid, acc_fuse);
@@ -2375,7 +2378,7 @@ int lob_theta_set(lob_engine* e, int32_t which, const double* host_in, int64_t c
         // the maps keep the bits they have (monotone: the tiles of live trace generations stay marked, whatever the
         // loaded value of their weights -- a set bit only means "fetch the weight") and gain those of the loaded non-zeros
         hipLaunchKernelGGL(rebuild_nzx_kernel, dim3(2048), dim3(256), 0, e->stream, (const f64*)th, e->S.theta_nzx, e->S.theta_nzc, e->P.cshift, e->P.M);
-        hipLaunchKernelGGL(rebuild_nzd_kernel, dim3(2048), dim3(256), 0, e->stream, (const uint32_t*)e->S.theta_nzx, e->S.theta_nzd, e->S.nzd_terms, e->P.M);
+        hipLaunchKernelGGL(rebuild_nzd_kernel, dim3(2048), dim3(256), 0, e->stream, (const uint32_t*)e->S.theta_nzx, e->S.theta_nzd, e->S.theta_nzm, e->S.nzd_terms, e->P.M);
         launch_memo(e, e->last_par, 1);  // the current triples under the loaded weights: the next act stays on the fast path
     }
     HIPCHK(hipGetLastError());
@@ -2545,7 +2548,7 @@ int lob_delta_apply(lob_engine* e) {
         TimedLaunch t(e, "delta_apply_kernel", nullptr, true);
         hipLaunchKernelGGL(delta_apply_kernel, dim3(2048), dim3(256), 0, e->stream, v ? e->S.theta_b : e->S.theta, e->S.theta_sync + v * M,
                            (const f64*)(e->S.delta + v * M), v ? e->S.theta_b_nz : e->S.theta_nz, e->S.nz_epoch, e->P.M,
-                           e->P.memo ? e->S.theta_nzx : (uint32_t*)nullptr, e->S.theta_nzc, e->P.cshift, e->S.theta_nzd, e->S.nzd_terms);
+                           e->P.memo ? e->S.theta_nzx : (uint32_t*)nullptr, e->S.theta_nzc, e->P.cshift, e->S.theta_nzd, e->S.theta_nzm, e->S.nzd_terms);
     }
     if (delta_extra(e))
         hipLaunchKernelGGL(rho_delta_apply_kernel, dim3(1), dim3(1), 0, e->stream, e->S.rho, e->S.theta_sync + M * nv, (const f64*)(e->S.delta + M * nv));
@@ -2670,7 +2673,7 @@ int lob_delta_sparse_apply(lob_engine* e) {
         TimedLaunch t(e, "delta_apply_kernel", nullptr, true);
         hipLaunchKernelGGL(sparse_apply_kernel, dim3(nb), dim3(LOB_SPX_BLOCK), 0, e->stream, (const uint32_t*)e->spx_union, (i64)W, (const i64*)e->spx_block_off,
                            e->S.theta, e->S.theta_sync, (const f64*)e->spx_buf, e->S.theta_nz, e->S.nz_epoch, e->S.theta_nzx, e->S.theta_nzc, e->P.cshift,
-                           e->S.theta_nzd, e->S.nzd_terms, (i64)e->P.M, (i64)e->spx_count);
+                           e->S.theta_nzd, e->S.theta_nzm, e->S.nzd_terms, (i64)e->P.M, (i64)e->spx_count);
     }
     if (e->P.memo && !mid_step) launch_memo(e, e->last_par, 1);  // the current triples under the exchanged weights
     HIPCHK(hipGetLastError());
@@ -2823,5 +2826,24 @@ extern "C" int lob_debug_new_weights(lob_engine* e, int32_t out[2]) {
     HIPCHK(hipMemcpyAsync(h, e->S.nz_new, sizeof(h), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     out[0] = h[0]; out[1] = h[LOB_NZ_WORDS];
+    return LOB_OK;
+}
+
+// Diagnostics (not part of include/lob_engine.h): the written-weights maps of the pair learn kernel as they stand once the stream
+// has drained -- the exact map [M / 32 + 1], the two maps folded over the actions [2][M / 32 + 1], the two tables of per-sum action
+// masks [2][2 * fold_mask_words(M)] (16 bits each; LOB_ESTATE when the plan keeps none) and the 18 action terms of groups 1 and 2.
+// The tests check the invariant between them: mask bit a of (g, s) = exact bit (s + term[g][a]) mod M, folded bit = mask != 0.
+extern "C" int lob_debug_fold_maps(lob_engine* e, uint32_t* nzx, uint32_t* nzd, uint16_t* nzm, uint32_t* terms18) {
+    if (!e || !nzx || !nzd || !nzm || !terms18) return LOB_EINVAL;
+    if (!e->S.theta_nzd || !e->S.theta_nzm) { lob_set_error("lob_debug_fold_maps: this engine keeps no action-mask table"); return LOB_ESTATE; }
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (e->stream2) HIPCHK(hipStreamSynchronize(e->stream2));
+    const size_t words = (size_t)e->P.M / 32 + 1, mwords = fold_mask_words((uint32_t)e->P.M);
+    HIPCHK(hipMemcpyAsync(nzx, e->S.theta_nzx, words * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(nzd, e->S.theta_nzd, 2 * words * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(nzm, e->S.theta_nzm, 2 * mwords * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(terms18, e->S.nzd_terms, 18 * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
     return LOB_OK;
 }

@@ -374,12 +374,21 @@ __device__ __forceinline__ void mark_generation(const DevParams& P, const DevSta
         w[4 * i + 0] = S.theta_nzx[(uint32_t)t[i].x >> 5]; w[4 * i + 1] = S.theta_nzx[(uint32_t)t[i].y >> 5];
         w[4 * i + 2] = S.theta_nzx[(uint32_t)t[i].z >> 5]; w[4 * i + 3] = S.theta_nzx[(uint32_t)t[i].w >> 5];
     }
+    // (which of the 32 still need their mark; then ONE copy of nzx_mark in a loop over those -- rare: 32 inlined copies of its
+    // read-modify-writes weighed on every instantiation of the env-step kernels)
+    uint32_t need = 0;
 #pragma unroll
     for (int i = 0; i < 8; i++) {
         const i32 f[4] = {t[i].x, t[i].y, t[i].z, t[i].w};
 #pragma unroll
         for (int k = 0; k < 4; k++)
-            if (!((w[4 * i + k] >> ((uint32_t)f[k] & 31)) & 1u)) nzx_mark(P, S, f[k]);
+            if (!((w[4 * i + k] >> ((uint32_t)f[k] & 31)) & 1u)) need |= 1u << (4 * i + k);
+    }
+#pragma unroll 1
+    while (need) {
+        const int i = __builtin_ctz(need);
+        need &= need - 1;
+        nzx_mark(P, S, reinterpret_cast<const i32*>(src)[i]);
     }
 }
 
@@ -1303,9 +1312,9 @@ __device__ __forceinline__ void ql_group(const DevParams& P, const DevState& S, 
 // One look-up per tiling instead of nine coarse-map reads: bit s of the group's theta_nzd map says whether ANY of the nine tiles
 // (s + term[a]) mod M of the tiling with hash sum s lies on a written weight.  The walk only hashes and tests that bit (the
 // words are requested a stage ahead); the few tilings that pass (7 % at 160 k written weights of 20 M) leave their sums in a
-// short per-lane list in LDS and are resolved afterwards, two at a time: nine exact-map words each, then the entries in
-// Agent::getQ's order (tilings ascending, actions ascending inside a tiling: what ql_consume produces).  No coarse image in
-// LDS: the block is small and several share a CU.
+// short per-lane list in LDS and are resolved afterwards, all at once: one 16-bit action mask each (lob_state.h theta_nzm, the
+// nine exact bits of the tiling kept per hash sum), then the entries in Agent::getQ's order (tilings ascending, actions
+// ascending inside a tiling: what ql_consume produces).  No coarse image in LDS: the block is small and several share a CU.
 #define LOB_QD_HCAP 12   /* tilings of one group that may pass per book (more: the general kernel takes the book) */
 template <int G, int VT, int CH>
 __device__ __forceinline__ void qd_issue(const DevParams& P, const DevState& S, const uint32_t* rnd, const int* q, int j0, uint32_t* sum_out, uint32_t* dw_out) {
@@ -1359,33 +1368,42 @@ __device__ __forceinline__ void ql_group_d(const DevParams& P, const DevState& S
     }
 #undef LOB_QD_TAKE
     if (nh > LOB_QD_HCAP) { n = CAP + 1; return; }  // (more tilings than the list holds: the general kernel)
-    // the tilings that passed, two per round: nine exact-map words each in flight together
+    // the tilings that passed: ONE 16-bit action mask each (theta_nzm: bit a = the exact bit of tile (s + term[a]) mod M), all of
+    // the lane's in flight together -- in chunks behind wave-uniform guards, so that a wave whose lanes have few issues few loads
+    const uint16_t* masks = reinterpret_cast<const uint16_t*>(+S.theta_nzm) + (G == 2 ? 2 * fold_mask_words(M) : 0);
+    constexpr int MC = 4;
+    static_assert(LOB_QD_HCAP % MC == 0, "whole chunks");
+    uint32_t mk[LOB_QD_HCAP];
+#pragma unroll
+    for (int c = 0; c < LOB_QD_HCAP; c += MC) {
+        if (__any(c < nh)) {
+#pragma unroll
+            for (int u = 0; u < MC; u++) mk[c + u] = c + u < nh ? (uint32_t)masks[hits[c + u]] : 0u;
+        } else {
+#pragma unroll
+            for (int u = 0; u < MC; u++) mk[c + u] = 0u;
+        }
+    }
+    // (the twelve 9-bit masks packed into two 64-bit registers -- [0..6] | [7..11] -- that the loop below shifts through: no
+    // register array indexed by the loop counter)
+    static_assert(LOB_QD_HCAP == 12 && LOB_N_ACTIONS == 9, "the packing below");
+    u64 plo = 0, phi = 0;
+#pragma unroll
+    for (int k = 0; k < 7; k++) plo |= (u64)mk[k] << (9 * k);
+#pragma unroll
+    for (int k = 7; k < LOB_QD_HCAP; k++) phi |= (u64)mk[k] << (9 * (k - 7));
+    // the entries in Agent::getQ's order: tilings ascending, actions ascending inside a tiling; tile indices of set bits only
 #pragma unroll 1
-    for (int k = 0; __any(k < nh); k += 2) {
-        const bool v0 = k < nh, v1 = k + 1 < nh;
-        const uint32_t s0 = v0 ? hits[k] : 0u, s1 = v1 ? hits[k + 1] : 0u;
-        i32 x0[LOB_N_ACTIONS], x1[LOB_N_ACTIONS];
-        uint32_t w0[LOB_N_ACTIONS], w1[LOB_N_ACTIONS];
-#pragma unroll
-        for (int a = 0; a < LOB_N_ACTIONS; a++) {
-            x0[a] = tile_index(s0, terms[a], M);
-            x1[a] = tile_index(s1, terms[a], M);
-            w0[a] = S.theta_nzx[v0 ? (uint32_t)x0[a] >> 5 : 0u];
-            w1[a] = S.theta_nzx[v1 ? (uint32_t)x1[a] >> 5 : 0u];
-        }
-#pragma unroll
-        for (int a = 0; a < LOB_N_ACTIONS; a++) {
-            if (v0 && ((w0[a] >> ((uint32_t)x0[a] & 31)) & 1u)) {
-                if (n < CAP) ql_put(row, 1 + n, x0[a], a, G == 2);
-                n++;
-            }
-        }
-#pragma unroll
-        for (int a = 0; a < LOB_N_ACTIONS; a++) {
-            if (v1 && ((w1[a] >> ((uint32_t)x1[a] & 31)) & 1u)) {
-                if (n < CAP) ql_put(row, 1 + n, x1[a], a, G == 2);
-                n++;
-            }
+    for (int k = 0; k < nh; k++) {
+        uint32_t m = (uint32_t)plo & 0x1ffu;
+        plo = (plo >> 9) | (phi << 54);
+        phi >>= 9;
+        const uint32_t s = hits[k];
+        while (m) {
+            const int a = __builtin_ctz(m);
+            m &= m - 1;
+            if (n < CAP) ql_put(row, 1 + n, tile_index(s, terms[a], M), a, G == 2);
+            n++;
         }
     }
 }

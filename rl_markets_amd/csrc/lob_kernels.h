@@ -913,23 +913,32 @@ __device__ inline i32 sel5(const i32* f, int k) {
 // Weight f of the shared theta is (about to be) written for the first time: the exact map and its coarse image
 // (lob_fast.h); monotone bits.  True if this call set the exact bit.
 // (the map folded over the actions, lob_state.h theta_nzd: the 18 hash sums whose tilings contain weight f)
-__device__ inline void nzd_mark(uint32_t* nzd, const uint32_t* terms18, uint32_t M, uint32_t f) {
+// ... and the per-sum action masks (theta_nzm; null: not kept), the action's bit BEFORE the folded bit of the same sum
+__device__ inline void nzd_mark(uint32_t* nzd, uint32_t* nzm, const uint32_t* terms18, uint32_t M, uint32_t f) {
     const size_t words = (size_t)M / 32 + 1;              // one map per tile group: [2][words]
-    // 18 independent read-modify-writes nobody waits for (the caller has just flipped the exact bit: once per weight)
-    uint32_t t[18];
+    const size_t mwords = fold_mask_words(M);             // ... and one mask table: [2][mwords]
+    // read-modify-writes nobody waits for (the caller has just flipped the exact bit: once per weight).  One round per tile group:
+    // its nine terms are requested together, and only nine sums are live at a time (NOTES.md "Round 8": what the other forms cost)
+#pragma unroll 1
+    for (int g = 0; g < 2; g++) {
+        uint32_t s[LOB_N_ACTIONS];
 #pragma unroll
-    for (int i = 0; i < 18; i++) t[i] = terms18[i];       // < M
+        for (int a = 0; a < LOB_N_ACTIONS; a++) s[a] = fold_sum(f, terms18[g * LOB_N_ACTIONS + a], M);   // (s + t) mod M == f, t < M
+        if (nzm) {
 #pragma unroll
-    for (int i = 0; i < 18; i++) {
-        const uint32_t s = f >= t[i] ? f - t[i] : f + (M - t[i]);  // (s + t) mod M == f
-        __hip_atomic_fetch_or(nzd + (i >= LOB_N_ACTIONS ? words : 0) + (s >> 5), 1u << (s & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int a = 0; a < LOB_N_ACTIONS; a++)
+                __hip_atomic_fetch_or(nzm + g * mwords + fold_mask_word(s[a]), (1u << a) << fold_mask_shift(s[a]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+#pragma unroll
+        for (int a = 0; a < LOB_N_ACTIONS; a++)
+            __hip_atomic_fetch_or(nzd + g * words + (s[a] >> 5), 1u << (s[a] & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 __device__ inline bool nzx_mark(const DevParams& P, const DevState& S, i32 f) {
     const uint32_t xb = 1u << ((uint32_t)f & 31);
     if (S.theta_nzx[(uint32_t)f >> 5] & xb) return false;
     const uint32_t old = atomicOr(&S.theta_nzx[(uint32_t)f >> 5], xb);
-    if (!(old & xb) && S.theta_nzd) nzd_mark(S.theta_nzd, S.nzd_terms, (uint32_t)P.M, (uint32_t)f);
+    if (!(old & xb) && S.theta_nzd) nzd_mark(S.theta_nzd, S.theta_nzm, S.nzd_terms, (uint32_t)P.M, (uint32_t)f);
     const uint32_t c = (uint32_t)f >> P.cshift;
     const uint32_t cb = 1u << (c & 31);
     if (!(S.theta_nzc[c >> 5] & cb)) atomicOr(&S.theta_nzc[c >> 5], cb);
@@ -2504,7 +2513,7 @@ __global__ void delta_begin_kernel(const f64* __restrict__ theta, const f64* __r
 #endif
 #if LOB_IN_MAIN
 __global__ void delta_apply_kernel(f64* theta, f64* sync, const f64* __restrict__ delta, uint32_t* nz, i32* nz_epoch, i64 M,
-                                   uint32_t* nzx, uint32_t* nzc, int cshift, uint32_t* nzd, const uint32_t* nzd_terms) {
+                                   uint32_t* nzx, uint32_t* nzc, int cshift, uint32_t* nzd, uint32_t* nzm, const uint32_t* nzd_terms) {
     i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0) atomicAdd(nz_epoch, 1);  // verdicts saved before this exchange are stale
     const i64 stride = (i64)gridDim.x * blockDim.x;
@@ -2520,7 +2529,7 @@ __global__ void delta_apply_kernel(f64* theta, f64* sync, const f64* __restrict_
                 const uint32_t xb = 1u << ((uint32_t)i & 31);
                 if (!(nzx[(uint32_t)i >> 5] & xb)) {
                     const uint32_t old = atomicOr(&nzx[(uint32_t)i >> 5], xb);
-                    if (!(old & xb) && nzd) nzd_mark(nzd, nzd_terms, (uint32_t)M, (uint32_t)i);
+                    if (!(old & xb) && nzd) nzd_mark(nzd, nzm, nzd_terms, (uint32_t)M, (uint32_t)i);
                 }
                 const uint32_t c = (uint32_t)i >> cshift;
                 if (!(nzc[c >> 5] & (1u << (c & 31)))) atomicOr(&nzc[c >> 5], 1u << (c & 31));
@@ -2617,7 +2626,7 @@ __global__ void __launch_bounds__(256) sparse_tail_kernel(f64* buf, const i64* _
 #if LOB_IN_MAIN
 __global__ void __launch_bounds__(LOB_SPX_BLOCK) sparse_apply_kernel(const uint32_t* __restrict__ u_map, i64 words, const i64* __restrict__ block_off,
                                                                      f64* theta, f64* sync, const f64* __restrict__ buf, uint32_t* nz, i32* nz_epoch,
-                                                                     uint32_t* nzx, uint32_t* nzc, int cshift, uint32_t* nzd, const uint32_t* nzd_terms, i64 M, i64 cap) {
+                                                                     uint32_t* nzx, uint32_t* nzc, int cshift, uint32_t* nzd, uint32_t* nzmask, const uint32_t* nzd_terms, i64 M, i64 cap) {
     __shared__ i32 lds[LOB_SPX_BLOCK / 64];
     const i64 w = (i64)blockIdx.x * LOB_SPX_BLOCK + threadIdx.x;
     if (w == 0) atomicAdd(nz_epoch, 1);  // verdicts saved before this exchange are stale
@@ -2643,7 +2652,7 @@ __global__ void __launch_bounds__(LOB_SPX_BLOCK) sparse_apply_kernel(const uint3
             if (nzd) {
                 uint32_t fresh = u0 & ~have;  // weights only other ranks have written so far
                 while (fresh) {
-                    nzd_mark(nzd, nzd_terms, (uint32_t)M, (uint32_t)((w << 5) + __builtin_ctz(fresh)));
+                    nzd_mark(nzd, nzmask, nzd_terms, (uint32_t)M, (uint32_t)((w << 5) + __builtin_ctz(fresh)));
                     fresh &= fresh - 1;
                 }
             }
@@ -2671,26 +2680,38 @@ __global__ void rebuild_nzx_kernel(const f64* __restrict__ theta, uint32_t* nzx,
 #endif
 // ... and the map folded over the actions from the exact one (gather form: no atomics; monotone like the exact map)
 #if LOB_IN_MAIN
-__global__ void rebuild_nzd_kernel(const uint32_t* __restrict__ nzx, uint32_t* nzd, const uint32_t* __restrict__ terms18, i64 M) {
+__global__ void rebuild_nzd_kernel(const uint32_t* __restrict__ nzx, uint32_t* nzd, uint32_t* nzm, const uint32_t* __restrict__ terms18, i64 M) {
     const i64 words = M / 32 + 1;
+    const size_t mwords = fold_mask_words((uint32_t)M);
     uint32_t t[18];
 #pragma unroll
     for (int i = 0; i < 18; i++) t[i] = terms18[i];
     for (i64 w = (i64)blockIdx.x * blockDim.x + threadIdx.x; w < words; w += (i64)gridDim.x * blockDim.x) {
         uint32_t out1 = 0, out2 = 0;
-        for (int k = 0; k < 32; k++) {
-            const i64 s = (w << 5) + k;
-            if (s >= M) break;
-            bool any1 = false, any2 = false;
+        for (int k = 0; k < 32; k += 2) {
+            // two sums a round: the two masks of one word of the mask table (this thread owns the words of its 32 sums)
+            uint32_t m1 = 0, m2 = 0;
+            for (int h = 0; h < 2; h++) {
+                const i64 s = (w << 5) + k + h;
+                if (s >= M) break;
+                uint32_t b1 = 0, b2 = 0;
 #pragma unroll
-            for (int i = 0; i < 18; i++) {
-                uint32_t f = (uint32_t)s + t[i];
-                if (f >= (uint32_t)M) f -= (uint32_t)M;   // (s, t < M < 2^31: no wrap of the 32-bit sum)
-                const bool hit = (nzx[f >> 5] >> (f & 31)) & 1u;
-                if (i < LOB_N_ACTIONS) any1 |= hit; else any2 |= hit;
+                for (int i = 0; i < 18; i++) {
+                    uint32_t f = (uint32_t)s + t[i];
+                    if (f >= (uint32_t)M) f -= (uint32_t)M;   // (s, t < M < 2^31: no wrap of the 32-bit sum)
+                    const uint32_t hit = (nzx[f >> 5] >> (f & 31)) & 1u;
+                    if (i < LOB_N_ACTIONS) b1 |= hit << i; else b2 |= hit << (i - LOB_N_ACTIONS);
+                }
+                m1 |= b1 << (16 * h);
+                m2 |= b2 << (16 * h);
+                out1 |= b1 ? 1u << (k + h) : 0u;
+                out2 |= b2 ? 1u << (k + h) : 0u;
             }
-            out1 |= any1 ? 1u << k : 0u;
-            out2 |= any2 ? 1u << k : 0u;
+            if (nzm && (w << 5) + k < M) {   // (the masks before the folded bits, as nzd_mark)
+                const size_t mw = fold_mask_word((uint32_t)((w << 5) + k));
+                if (m1 & ~nzm[mw]) nzm[mw] |= m1;
+                if (m2 & ~nzm[mwords + mw]) nzm[mwords + mw] |= m2;
+            }
         }
         if (out1 & ~nzd[w]) nzd[w] |= out1;   // (this thread owns the words)
         if (out2 & ~nzd[words + w]) nzd[words + w] |= out2;

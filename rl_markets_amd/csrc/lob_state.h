@@ -372,6 +372,12 @@ struct DevState {
     // answers "does any of this tiling's nine tiles lie on a written weight" with one look-up instead of nine (93 % of the
     // tilings: none, at 160 k written weights of 20 M).  Set with the exact bit, wherever that is set (nzd_mark).
     GP<uint32_t> theta_nzd;      // [2: tile group 1, 2][M / 32 + 1]
+    // ... and WHICH of the nine: a 16-bit mask per hash sum and group, bit a = theta_nzx[(s + term[g][a]) mod M], kept at the
+    // same sites as the folded bit and written BEFORE it (nzd_mark), so that a set folded bit never points at a mask that knows
+    // less than the exact map did when the bit was set.  The pair kernel resolves a passed tiling with this one load instead of
+    // nine exact-map words.  Two masks per word (lob_tiles.h fold_mask_*); 80 MB at M = 20 M; null unless the plan can select
+    // the pair kernel -- the folded map, 2 x 2.5 MB and mostly L2-resident, stays the first level.
+    GP<uint32_t> theta_nzm;      // [2][fold_mask_words(M)]
     GP<const uint32_t> nzd_terms; // [18]: term[1][0..8], term[2][0..8] (the engine's hash table + 2048 + 9)
     GP<i32> tr_list;        // [B] books the lane-per-book trace kernel leaves to the wave-per-book one
     GP<i32> tr_list_n;      // [2 parities]

@@ -60,6 +60,15 @@ __device__ inline i32 tile_index(uint32_t base_m, uint32_t term_m, uint32_t M) {
     return (i32)(s >= M ? s - M : s);
 }
 
+// The maps folded over the actions (lob_state.h theta_nzd, theta_nzm) are indexed by the hash sum s of a tiling, not by the
+// weight: weight f is tile (s, action a) of group g for the ONE sum s with (s + term[g][a]) mod M == f  (f, term < M < 2^31).
+__host__ __device__ inline uint32_t fold_sum(uint32_t f, uint32_t term_m, uint32_t M) { return f >= term_m ? f - term_m : f + (M - term_m); }
+// theta_nzm: one 16-bit action mask per (group, sum), two masks per 32-bit word (the marks are 32-bit atomics), each group's
+// table padded to whole words: [2][fold_mask_words(M)] words = [2][2 * fold_mask_words(M)] masks.
+__host__ __device__ inline size_t fold_mask_words(uint32_t M) { return ((size_t)M + 1) >> 1; }
+__host__ __device__ inline size_t fold_mask_word(uint32_t s) { return (size_t)(s >> 1); }
+__host__ __device__ inline uint32_t fold_mask_shift(uint32_t s) { return (s & 1u) << 4; }
+
 // Two group-0 triples (quantised coordinates a, b; every coordinate >= LOB_TILE_PLAIN_MIN: tile_coord's plain branch) fall in
 // the same cell of tiling j when, for the three coordinates i, the cell numbers ((q_i - (1 + 2 i) j) >> 5) agree mod 64: the
 // hash reads the cell's coordinate & 2047 (tile_base_m), so two tiles of one tiling and one action whose cells agree that

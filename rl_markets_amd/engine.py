@@ -471,6 +471,18 @@ class Engine:
                 "list_len_p50": pct(0.5), "list_len_p99": pct(0.99), "list_len_max": int(np.nonzero(hist)[0].max()) if with_list else None,
                 "hist": hist}
 
+    def fold_maps(self):
+        """lob_debug_fold_maps (a diagnostic export): the pair learn kernel's written-weights maps after a stream synchronisation --
+        exact map [M/32+1] u32, folded maps [2][M/32+1] u32, action masks [2][M] u16 (the padding of an odd M cut off), terms [2][9]."""
+        M = int(self.M)
+        words, mstride = M // 32 + 1, 2 * ((M + 1) // 2)
+        nzx, nzd = np.zeros(words, np.uint32), np.zeros((2, words), np.uint32)
+        nzm, terms = np.zeros((2, mstride), np.uint16), np.zeros((2, 9), np.uint32)
+        fn = self.lib.lob_debug_fold_maps
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p] * 5
+        self._check(fn(self.h, _ptr(nzx), _ptr(nzd), _ptr(nzm), _ptr(terms)))
+        return {"exact": nzx, "folded": nzd, "masks": nzm[:, :M], "terms": terms}
+
     # ---- multi-GPU weight exchange ----
     def delta_init(self):
         self._check(self.lib.lob_delta_init(self.h))
