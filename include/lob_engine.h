@@ -513,6 +513,49 @@ int lob_snapshot_save(lob_engine* e, int32_t slot, const uint8_t* dev_mask);
 int lob_snapshot_restore(lob_engine* e, int32_t slot, const uint8_t* dev_mask);
 int lob_snapshot_free(lob_engine* e, int32_t slot);
 
+/* ---- vector-env interface: the engine's own Q values and policy actions, on the device ---
+ * The one agent the interface above could not use: the engine's own tile-coded linear-Q agent.  lob_vec_act stands in for
+ * Agent::getQ, Agent::action and Greedy::Sample / EpsilonGreedy::Sample / Boltzmann::Sample (src/rl/agent.cpp:117-169, 196-204;
+ * src/rl/policy.cpp:37-117) over the whole batch, from device memory to device memory: lob_vec_act then lob_vec_step(action) is one
+ * agent step of the engine's policy -- as a teacher, a baseline, an opponent or an epsilon-mix partner of a network on the same GPU,
+ * and on books that lob_snapshot_restore has put back, where lob_eval_step and lob_td_step are refused.
+ *   lob_vec_act_out: where the results go, DEVICE pointers on the engine's GPU, written in stream order; a NULL member is skipped.
+ * ONE rule for EVERY book b, whatever its `terminal` value:
+ *     q[b][a] = Agent::getQ(a) on the book's latest getState() vector -- the row lob_vec_step wrote to obs -- under the weights that
+ *     book's agent uses (theta of book b under LOB_THETA_PRIVATE); for the double agents (LOB_ALGO_DOUBLE_Q, LOB_ALGO_DOUBLE_R_LEARN)
+ *     (Qa + Qb) / 2.0, as DoubleAgent::action forms it.  Bit for bit the sum the reference computes; every element is written on
+ *     every call.
+ *     action[b], a live book (lob_get_terminal == 0): the mode's choice among q[b][.].  A sample is drawn from the book's own policy
+ *     stream at its counter (lob_get_rng_counters) and the new counter is written back -- the draws lob_eval_step / lob_td_step make
+ *     for the same values; that counter is the only word of engine state the call writes.
+ *     action[b], a book with terminal != 0: 0, and nothing is drawn (lob_vec_step never counts it as out of range).
+ *     action == NULL: nothing is sampled and no counter moves, in any mode.
+ *   Modes:
+ *     LOB_ACT_GREEDY     Agent::GoGreedy() then Agent::action -- what lob_eval_step plays: Greedy::Sample, ties among the maxima
+ *                        broken by draws from the book's stream (none without a tie);
+ *     LOB_ACT_BEHAVIOUR  the learner's behaviour policy at the current epsilon / tau (lob_set_epsilon, lob_set_tau): epsilon-greedy
+ *                        or Boltzmann;
+ *     LOB_ACT_ARGMAX     the lowest index among the maxima.  It draws nothing and changes not one byte of engine state.
+ *   Nothing else changes: the learner's record of the last step, its verdicts, traces, written-weights maps and memo tables, the
+ * step headers' action / stepped words and the counters of lob_get_counters stay as they are.
+ *   lob_vec_act: enqueued on the engine's stream (lob_stream), returns at once -- no host read, no allocation, no copy and no
+ * synchronisation.  Valid whenever lob_vec_book is, also after lob_snapshot_restore.  LOB_EINVAL for a NULL engine, a NULL out or a
+ * mode outside 0..2; a struct whose two members are both NULL is LOB_OK and launches nothing.  LOB_ESTATE before the first lob_reset
+ * and between lob_td_step_begin and lob_td_step_end.
+ *   lob_vec_q: the device form of lob_q_values, for n free-standing states.  dev_vars: f32 [n][n_vars], dev_q: f64 [n][LOB_N_ACTIONS],
+ * both in device memory on the engine's GPU.  The weights are the ones lob_q_values uses (theta; book 0's under private theta; Qa
+ * only) and the output is bit for bit what it returns for the same rows.  Needs no lob_reset; enqueued like lob_vec_act, with no
+ * allocation and no synchronisation.  LOB_EINVAL for a NULL engine or pointer, or n < 1. */
+#define LOB_ACT_GREEDY    0
+#define LOB_ACT_BEHAVIOUR 1
+#define LOB_ACT_ARGMAX    2
+typedef struct lob_vec_act_out {   /* DEVICE pointers on the engine's GPU; any may be NULL = not wanted */
+    int32_t* action;   /* [n_books] */
+    double*  q;        /* [n_books][LOB_N_ACTIONS]: the values the policy looked at */
+} lob_vec_act_out;
+int lob_vec_act(lob_engine* e, int32_t mode, const lob_vec_act_out* out);
+int lob_vec_q(lob_engine* e, const float* dev_vars, int32_t n, double* dev_q);
+
 /* ---- episode statistics of the whole batch ---------------------------------
  * What the reference logs about ONE environment after an episode -- the `training_log` row of Runner::RunEpisode
  * (src/experiment/serial.cpp:81-88: getEpisodeReward, getEpisodePnL, total_ticks), Base::writeStats and getTotalTransactions

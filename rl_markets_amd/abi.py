@@ -167,6 +167,15 @@ class VecHistOut(C.Structure):
 # lob_snapshot_*: the snapshot slots of an engine (LOB_MAX_SNAPSHOTS)
 MAX_SNAPSHOTS = 4
 
+# lob_vec_act: the modes (LOB_ACT_*) -- what lob_eval_step plays, the learner's behaviour policy, the first maximum with no draw
+ACT_GREEDY, ACT_BEHAVIOUR, ACT_ARGMAX = 0, 1, 2
+
+
+class VecActOut(C.Structure):
+    """lob_vec_act_out: where lob_vec_act writes, two DEVICE addresses (0 = not wanted)."""
+    _fields_ = [("action", C.c_void_p), ("q", C.c_void_p)]
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LOB_ENGINE_LIB: an experiment build of the same library (tools/exp_prof.py, tools/exp_variants.sh)
 LIB_PATH = os.environ.get("LOB_ENGINE_LIB") or os.path.join(_HERE, "csrc", "liblob_engine.so")
@@ -237,6 +246,8 @@ def load():
         "lob_vec_status": (C.c_int, [vp, P(C.c_int64)]),
         "lob_vec_book": (C.c_int, [vp, P(VecBookOut)]),
         "lob_vec_history": (C.c_int, [vp, C.c_int32, P(VecHistOut)]),
+        "lob_vec_act": (C.c_int, [vp, C.c_int32, P(VecActOut)]),
+        "lob_vec_q": (C.c_int, [vp, vp, C.c_int32, vp]),
         "lob_snapshot_save": (C.c_int, [vp, C.c_int32, C.c_void_p]),
         "lob_snapshot_restore": (C.c_int, [vp, C.c_int32, C.c_void_p]),
         "lob_snapshot_free": (C.c_int, [vp, C.c_int32]),

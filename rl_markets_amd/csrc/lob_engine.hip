@@ -1535,6 +1535,47 @@ int lob_vec_history(lob_engine* e, int32_t K, const lob_vec_hist_out* out) {
     return LOB_OK;
 }
 
+// The engine's own Q values and policy actions for every book, into the caller's device buffers (lob_tu_vecact.hip vec_act_kernel;
+// DESIGN.md 7h): one launch on the engine's stream, nothing read back.  The kernel reads the state through its device-resident copy,
+// which the first lob_reset has uploaded (sync_state); every array it follows from there is allocated by lob_create and stays.
+// Not refused after lob_snapshot_restore: it reads the books' latest getState(), which the restore put back, and nothing of the
+// learner's memory of the last transition.
+int lob_vec_act(lob_engine* e, int32_t mode, const lob_vec_act_out* out) {
+    if (!e || !out) { lob_set_error("lob_vec_act: NULL argument"); return LOB_EINVAL; }
+    if (mode < LOB_ACT_GREEDY || mode > LOB_ACT_ARGMAX) { lob_set_error("lob_vec_act: mode " + std::to_string(mode) + " is none of LOB_ACT_GREEDY, LOB_ACT_BEHAVIOUR, LOB_ACT_ARGMAX"); return LOB_EINVAL; }
+    int rc = need_reset(e, "lob_vec_act");
+    if (rc) return rc;
+    if ((rc = not_mid_step(e, "lob_vec_act"))) return rc;
+    if (!out->action && !out->q) return LOB_OK;
+    HIPCHK(hipSetDevice(e->device));
+    VecActSrc a;
+    a.rows = nullptr; a.theta = nullptr; a.nz = nullptr;
+    a.n = e->B; a.mode = mode;
+    a.action = out->action; a.q = out->q;
+    {
+        TimedLaunch t(e, "vec_act_kernel", nullptr, true);
+        lobk_vec_act(e->stream, e->P.algo == LOB_ALGO_DOUBLE_Q, e->n_cus, LOB_PS(e), (const uint32_t*)e->rnd_dev, a);
+    }
+    HIPCHK(hipGetLastError());
+    return LOB_OK;
+}
+
+// lob_q_values with both ends in device memory: the same kernel over the caller's rows, under theta (book 0's under private theta).
+int lob_vec_q(lob_engine* e, const float* dev_vars, int32_t n, double* dev_q) {
+    if (!e || !dev_vars || !dev_q || n < 1) { lob_set_error("lob_vec_q: bad argument"); return LOB_EINVAL; }
+    HIPCHK(hipSetDevice(e->device));
+    VecActSrc a;
+    a.rows = dev_vars; a.theta = (const f64*)e->S.theta; a.nz = (const uint32_t*)e->S.theta_nz;
+    a.n = n; a.mode = LOB_ACT_ARGMAX;
+    a.action = nullptr; a.q = dev_q;
+    {
+        TimedLaunch t(e, "vec_q_kernel", nullptr, true);
+        lobk_vec_act(e->stream, false, e->n_cus, LOB_PS(e), (const uint32_t*)e->rnd_dev, a);
+    }
+    HIPCHK(hipGetLastError());
+    return LOB_OK;
+}
+
 // ---- book snapshots (include/lob_engine.h lob_snapshot_*; lob_tu_snapshot.hip) ----
 // The descriptor table of the arrays a snapshot holds and their places in a slot buffer, built once per engine with the first save:
 // every array of LOB_ENV_FIELDS, the rolling means pnl_ups / pnl_downs, then the per-book records (LHdr's five environment words,

@@ -1,6 +1,7 @@
-// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is ten
+// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is eleven
 // .hip files built in parallel: lob_engine.hip -- the C ABI's host side and the update / memo / trace kernels --, lob_tu_env.hip,
-// lob_tu_prepass.hip, lob_tu_learn.hip, lob_tu_stats.hip, lob_tu_steplog.hip, lob_tu_vec.hip, lob_tu_vecbook.hip, lob_tu_vechist.hip, lob_tu_snapshot.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
+// lob_tu_prepass.hip, lob_tu_learn.hip, lob_tu_stats.hip, lob_tu_steplog.hip, lob_tu_vec.hip, lob_tu_vecbook.hip, lob_tu_vechist.hip, lob_tu_snapshot.hip,
+// lob_tu_vecact.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
 // lob_engine.hip used when it held the launches itself.  Kernels measured and lost (NOTES.md "Round 4") are only compiled with
 // -DLOB_EXPERIMENTS (tools/exp_variants.sh); a product build answers LOB_EXPERIMENTS-only requests with the product kernel.
 #ifndef LOB_LAUNCH_H
@@ -168,6 +169,25 @@ struct SnapArgs {
 };
 // snapshot_masked_kernel (dev_mask: uint8 [B] in device memory, nonzero selects) or, dev_mask == NULL, snapshot_all_kernel
 void lobk_snapshot(hipStream_t st, bool restore, const SnapArgs& a, void* slot, const uint8_t* dev_mask);
+
+// ---- lob_tu_vecact.hip ----
+// What lob_vec_act / lob_vec_q (include/lob_engine.h) read and write beyond the parameters and the state, which vec_act_kernel takes by
+// pointer (lob_state.h LOB_PS_ARGS): the caller's device buffers, the mode and -- for free-standing states -- the rows and the one
+// weight vector with its "ever written" map, so that this form reads nothing of the state (valid before the first lob_reset, when the
+// state's device-resident copy has not been uploaded yet).
+#define LOB_VECACT_MAX_BLOCKS 2048
+struct VecActSrc {
+    const f32* rows;       // free-standing states [n][V] (null: the books' latest getState(), slot 2 of DevState::vars)
+    const f64* theta;      // free-standing states: the weights lob_q_values uses ...
+    const uint32_t* nz;    // ... and their map
+    i32 n;                 // states: the books, or the caller's rows
+    i32 mode;              // LOB_ACT_*
+    i32* action;           // [n] (null: nothing is sampled)
+    f64* q;                // [n][LOB_N_ACTIONS] (null: not wanted)
+};
+// vec_act_kernel<books, dq>: a persistent grid of at most LOB_VECACT_MAX_BLOCKS blocks, sized from the compute units (`n_cus`); `dq`: the
+// double agents' second weight vector (the books' form only: a.rows null)
+void lobk_vec_act(hipStream_t st, bool dq, int n_cus, const DevParams* Pd, const DevState* Sd, const uint32_t* rnd, const VecActSrc& a);
 
 // ---- lob_tu_learn.hip ----
 // learn_q_pair_kernel / learn_q_lane_kernel<algo, vt, tr>: vt = 8 when the state has eight variables (else 0)

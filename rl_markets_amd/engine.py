@@ -302,6 +302,18 @@ class Engine:
         enqueued on the engine's stream."""
         self._check(self.lib.lob_vec_history(self.h, int(K), C.byref(out)))
 
+    def vec_act(self, mode, out):
+        """lob_vec_act: Q(s, .) of every book's latest getState() under the engine's own weights and the action its policy takes there
+        (mode abi.ACT_GREEDY: what eval_step plays; abi.ACT_BEHAVIOUR: the learner's epsilon-greedy / Boltzmann policy;
+        abi.ACT_ARGMAX: the first maximum, nothing drawn), written to the device buffers of `out` (abi.VecActOut: action int32 [B],
+        q f64 [B, 9]); enqueued on the engine's stream.  Works after snapshot_restore() as well."""
+        self._check(self.lib.lob_vec_act(self.h, int(mode), C.byref(out)))
+
+    def vec_q(self, vars_ptr, n, q_ptr):
+        """lob_vec_q: q_values() with both ends in device memory -- f32 [n, n_vars] at `vars_ptr` in, f64 [n, 9] at `q_ptr` out;
+        enqueued on the engine's stream."""
+        self._check(self.lib.lob_vec_q(self.h, C.c_void_p(vars_ptr), int(n), C.c_void_p(q_ptr)))
+
     def snapshot_save(self, slot, mask_ptr=None):
         """lob_snapshot_save: the environment state of the books selected by the DEVICE mask at address `mask_ptr` (uint8 [B],
         nonzero selects; None: every book, which (re)starts the slot) into snapshot slot `slot` (0 .. abi.MAX_SNAPSHOTS - 1);

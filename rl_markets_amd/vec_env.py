@@ -33,6 +33,13 @@ returns the refreshed `obs` (and refreshes the book / history tensors).  Per-boo
 A snapshot belongs to its episode (reset() voids it), and after a restore the engine's own learner calls (td_step, eval_step) are
 refused until the next reset().  A VecEnv that never calls save() / restore() launches and allocates nothing for them.
 
+act(mode) asks the engine's own tile-coded linear-Q agent (lob_vec_act): it returns .act_actions, int32 [B], the action its policy
+takes on every book's latest observation -- "greedy" (what eval_step plays), "behaviour" (the learner's epsilon-greedy / Boltzmann
+policy at the current epsilon / tau) or "argmax" (the first maximum, no random draw) --, and leaves the values it looked at in .act_q,
+f64 [B, 9].  env.step(env.act()) is one agent step of the engine's greedy policy, with no host in it; it also works on books that
+restore() has put back.  q_values(vars) evaluates the same weights on any f32 [n, V] tensor of states (lob_vec_q).  A VecEnv that
+never calls act() allocates and launches nothing for it.
+
 step() reads the actions from the tensor's device memory and writes into five persistent tensors (lob_vec_step,
 include/lob_engine.h): no copy to or from the host and no synchronisation.  The engine runs on a stream of its own; it is made
 to wait for torch's current stream before the call (the actions are ready) and torch's current stream for the engine's after it
@@ -75,6 +82,7 @@ class VecEnv:
             self.hist_rec = torch.zeros(self.B, dtype=torch.int32, device=dev)
             self.hist_out = abi.VecHistOut(self.hist_levels.data_ptr(), self.hist_trades.data_ptr(), self.hist_time_ms.data_ptr(),
                                            self.hist_valid.data_ptr(), self.hist_rec.data_ptr())
+        self.act_actions = self.act_q = self.act_out = None   # (allocated by the first act())
         self.stream = torch.cuda.ExternalStream(eng.lob_stream(), device=dev)
         self.bad_actions = 0
         # (the zero fills above ran on torch's stream: the engine's first write must come after them)
@@ -112,6 +120,38 @@ class VecEnv:
         # record an event on when the tensor is freed -- possibly after Engine.close() has destroyed that stream.
         actions.record_stream(cur)
         return self.obs, self.reward, self.terminal, self.stepped
+
+    _ACT_MODES = {"greedy": abi.ACT_GREEDY, "behaviour": abi.ACT_BEHAVIOUR, "argmax": abi.ACT_ARGMAX}
+
+    def act(self, mode="greedy"):
+        """lob_vec_act: the engine's own policy on every book's latest observation.  Returns .act_actions (int32 [B], persistent; 0
+        for a book that is over); .act_q (f64 [B, 9]) holds the values it chose among.  "greedy" and "behaviour" draw from the books'
+        own policy streams, as eval_step / td_step do; "argmax" draws nothing."""
+        if mode not in self._ACT_MODES:
+            raise ValueError("VecEnv.act: mode must be one of %s" % ", ".join(sorted(self._ACT_MODES)))
+        cur = torch.cuda.current_stream(self.device)
+        if self.act_out is None:
+            self.act_actions = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+            self.act_q = torch.zeros((self.B, abi.LOB_N_ACTIONS), dtype=torch.float64, device=self.device)
+            self.act_out = abi.VecActOut(self.act_actions.data_ptr(), self.act_q.data_ptr())
+        self.stream.wait_stream(cur)      # (the zero fills, and whoever still reads the tensors of the last act())
+        self.eng.vec_act(self._ACT_MODES[mode], self.act_out)
+        cur.wait_stream(self.stream)
+        return self.act_actions
+
+    def q_values(self, vars):
+        """lob_vec_q: Q(s, .) under the engine's weights (theta; book 0's under private theta) for n free-standing states, f32 [n, V]
+        on the engine's device -> a new f64 [n, 9] tensor; bit for bit Engine.q_values of the same rows."""
+        if (not isinstance(vars, torch.Tensor) or vars.dtype != torch.float32 or not vars.is_cuda or vars.device != self.device
+                or vars.dim() != 2 or vars.shape[1] != self.V or vars.shape[0] < 1 or not vars.is_contiguous()):
+            raise ValueError("VecEnv.q_values: vars must be a contiguous float32 CUDA tensor of shape (n, %d) on the engine's device" % self.V)
+        q = torch.empty((vars.shape[0], abi.LOB_N_ACTIONS), dtype=torch.float64, device=self.device)
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)      # the rows are ready
+        self.eng.vec_q(vars.data_ptr(), vars.shape[0], q.data_ptr())
+        cur.wait_stream(self.stream)
+        vars.record_stream(cur)           # (as step() does with the actions)
+        return q
 
     def _mask_ptr(self, mask, who):
         if mask is None:

@@ -12,8 +12,8 @@ if "--csv" in sys.argv:
     i = sys.argv.index("--csv")
     csv_path = sys.argv[i + 1]
     del sys.argv[i:i + 2]
-# (the library's ten device translation units, rl_markets_amd/csrc/lob_launch.h, compiled side by side)
-units = ["lob_engine.hip", "lob_tu_env.hip", "lob_tu_prepass.hip", "lob_tu_learn.hip", "lob_tu_stats.hip", "lob_tu_steplog.hip", "lob_tu_vec.hip", "lob_tu_vecbook.hip", "lob_tu_vechist.hip", "lob_tu_snapshot.hip"]
+# (the library's eleven device translation units, rl_markets_amd/csrc/lob_launch.h, compiled side by side)
+units = ["lob_engine.hip", "lob_tu_env.hip", "lob_tu_prepass.hip", "lob_tu_learn.hip", "lob_tu_stats.hip", "lob_tu_steplog.hip", "lob_tu_vec.hip", "lob_tu_vecbook.hip", "lob_tu_vechist.hip", "lob_tu_snapshot.hip", "lob_tu_vecact.hip"]
 procs = [subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "--cuda-device-only", "-c",
                            "-Rpass-analysis=kernel-resource-usage", "-Wno-unused-value", "-o", "/dev/null", u] + sys.argv[1:],
                           cwd=CSRC, stderr=subprocess.PIPE, stdout=subprocess.PIPE, text=True) for u in units]
@@ -43,7 +43,7 @@ for line in filt.splitlines():
                          cur.get("VGPRs Spill"), cur.get("ScratchSize [bytes/lane]"), cur.get("Occupancy [waves/SIMD]"), cur.get("LDS Size [bytes/block]")))
 if csv_path:
     with open(csv_path, "w") as fh:
-        fh.write("# hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage of the four translation units of rl_markets_amd/csrc (tools/kernel_resources.py);"
+        fh.write("# hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage of the device translation units of rl_markets_amd/csrc (tools/kernel_resources.py);"
                  " occupancy = waves per SIMD the register / LDS budget allows; dynamic LDS (the fast learner kernels) is not included\n")
         fh.write("kernel,vgprs,agprs,sgprs,sgprs_spilled,vgprs_spilled,scratch_bytes_per_lane,occupancy_waves_per_simd,static_lds_bytes_per_block\n")
         for r in rows:
