@@ -260,7 +260,10 @@ void lob_default_gen_params(lob_gen_params* g);
 int lob_gen_stream_host(const lob_gen_params* g, int32_t depth, int32_t max_trades,
                         uint64_t first_book_id, int32_t n_books, uint32_t* out);
 /* Check a host stream against the engine preconditions (positive prices and
- * volumes, strictly monotone price keys per side, ascending trade prices). */
+ * volumes, strictly monotone price keys per side, ascending trade prices, and no more than max_trades distinct trade price
+ * keys in the rows whose trades one event merges: those after the previous event's first row up to its own first row, where
+ * a row ends an event when the next row's time differs and the book it leaves is a valid state -- otherwise a step would end in
+ * "more trade price levels in one event than max_trades"). */
 int lob_validate_stream(const uint32_t* records, int32_t depth, int32_t max_trades,
                         int32_t n_books, int32_t n_events);
 

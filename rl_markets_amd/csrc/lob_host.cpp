@@ -214,11 +214,44 @@ int lob_gen_stream_host(const lob_gen_params* g, int32_t D, int32_t T, uint64_t 
 static int validate_book(const uint32_t* rec, int32_t D, int32_t T, int b, int32_t n_events, char* buf, size_t cap) {
     const int W = lob_rec_words(D, T);
     int32_t last_t = -1;
+    // The trade list of one NextState is merged from the rows after the previous event's first row up to its own first row, and
+    // the engine holds it in max_trades slots (LOB_ERR_TRADE_OVERFLOW).  A row ends its event when the next row's time differs
+    // and it leaves a valid state (IsValidState: not crossed, a mid-price move below the mid-price) -- a property of the
+    // stream alone, so the rows that merge are known here: `keys` = the distinct 1e-4 keys since the last event's first row.
+    double keys[LOB_MAX_TRADES];
+    int n_keys = 0, group_from = 0;
+    bool prev_ends = true;      // the row before this one ended an event (or there is none): this row is an event's first
+    double stash_mid = 0.0;     // the mid-price the running event started from (0: none yet)
     for (int e = 0; e < n_events; e++) {
         const uint32_t* r = rec + ((size_t)b * n_events + e) * W;
         int32_t t = (int32_t)r[LOB_REC_TIME];
         if (t < last_t) { snprintf(buf, cap, "book %d event %d: time goes backwards", b, e); return LOB_EDATA; }
         last_t = t;
+        for (int i = 0; i < T; i++) {
+            const int32_t v = (int32_t)r[lob_rec_trade_vol(D, T) + i];
+            const double p = lob_bits_f32(r[lob_rec_trade_px(D, T) + i]);
+            if (v <= 0 || !(p > 0.0)) continue;   // (an empty slot; anything else is refused below)
+            const double k = rint(p * 10000.0);
+            bool found = false;
+            for (int q = 0; q < n_keys; q++) found = found || keys[q] == k;
+            if (found) continue;
+            if (n_keys >= T) {
+                snprintf(buf, cap, "book %d event %d: the trades of events %d..%d are merged into one event's list (same-timestamp rows, invalid "
+                         "states) and have more than max_trades = %d distinct price keys", b, e, group_from, e, T);
+                return LOB_EDATA;
+            }
+            keys[n_keys++] = k;
+        }
+        {
+            const bool first_of_event = prev_ends;
+            const double ap0 = lob_bits_f32(r[lob_rec_ask_px(D, T)]), bp0 = lob_bits_f32(r[lob_rec_bid_px(D, T)]);
+            const double mid = (ap0 + bp0) / 2.0;
+            const bool valid = stash_mid == 0.0 || (ap0 - bp0 >= 0.0 && mid > 0.0 && fabs(mid - stash_mid) < mid);
+            const bool same_next = e + 1 < n_events && (int32_t)rec[((size_t)b * n_events + e + 1) * W + LOB_REC_TIME] == t;
+            prev_ends = valid && !same_next;
+            if (prev_ends) stash_mid = mid;
+            if (first_of_event) { n_keys = 0; group_from = e + 1; }   // this row closed the list of its own event
+        }
         double pa = 0, pb = 1e300;
         for (int l = 0; l < D; l++) {
             double ap = lob_bits_f32(r[lob_rec_ask_px(D, T) + l]), bp = lob_bits_f32(r[lob_rec_bid_px(D, T) + l]);

@@ -5,6 +5,17 @@
 // thrown at random rows and trade lists (prices on the tick grid around the touch so that keys collide, volumes
 // that grow and shrink, queue positions incl. the negative q_tail of quirk Q2, zero totals -> the x86 cvttsd2si
 // corner); after every pass the complete EnvR and StepAgg of both must be bit-identical.
+// The rows also do what vendor files do (tests/hard_streams.py makes the same of whole streams for the GPU):
+//   off-grid   level prices one float off the grid (mostly the same 1e-4 key with other bits; a move that would give
+//              two levels of a side one key is not made: lob_validate_stream refuses such a row);
+//   shifted    a row several ticks away from the row before it: orders left far behind, or crossed by the book;
+//   crossed    rows with the two sides swapped and reversed: an invalid state, so the event runs on through them --
+//              as the middle row of a three-row event, or a run of them.  RESTRICTED to what the dispatch guarantees:
+//              the pre-pass ends an event only at a row that leaves a valid state, so an event's LAST row (the touch
+//              and mid-price of the track entry) is never crossed, nor is the row a step starts from;
+//   deep       trades at level 3..D of the row before, or beyond its last level.
+// An event is as many rows as the stream says: it runs on while its row is crossed, or (one in six) "has the next
+// row's timestamp".
 //   g++ -std=c++17 -O1 -ffp-contract=off -Itests/host_env/shim -o pass_diff tests/host_env/pass_diff.cpp && ./pass_diff [cases]
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -32,7 +43,7 @@ static double ru() { return (double)(rng() >> 11) * (1.0 / 9007199254740992.0); 
 
 int main(int argc, char** argv) {
     const long cases = argc > 1 ? atol(argv[1]) : 200000;
-    long n_pass = 0, n_fill = 0, n_cancel = 0, n_adverse = 0, n_multi = 0;
+    long n_pass = 0, n_fill = 0, n_cancel = 0, n_adverse = 0, n_multi = 0, n_offgrid = 0, n_shift = 0, n_crossed = 0, n_crossed_mid = 0, n_deep = 0;
     for (long cs = 0; cs < cases; cs++) {
         DevParams P;
         memset(&P, 0, sizeof P);
@@ -44,7 +55,9 @@ int main(int argc, char** argv) {
         P.damping_factor = (float)ru(); P.pos_weight = (float)(2 * ru()); P.pnl_weight = (float)(2 * ru());
         P.open_ms = 8 * 3600000LL; P.close_ms = 16 * 3600000LL + 1800000LL;
         // a little stream of rows on a 0.1 / 0.0001 / 0.5 grid
-        const int n_rows = 12;
+        const int n_rows = 16;
+        bool r_off[n_rows] = {}, r_shift[n_rows] = {}, r_cross[n_rows] = {}, r_deep[n_rows] = {};
+        int prev_bid = 0, prev_spread = 1;
         const double tick = ri(0, 2) == 0 ? 0.1 : (ri(0, 1) ? 0.0001 : 0.5);
         const int base = ri(200, 90000);
         std::vector<uint32_t> rows((size_t)n_rows * P.Wd, 0);
@@ -53,6 +66,7 @@ int main(int argc, char** argv) {
             uint32_t rec[64];
             memset(rec, 0, sizeof rec);
             bid_tick += ri(-1, 1);
+            if (r > 0 && ri(0, 7) == 0) { bid_tick += (ri(0, 1) ? 1 : -1) * ri(2, 6); r_shift[r] = true; }
             const int spread = ri(1, 2);
             rec[LOB_REC_TIME] = (uint32_t)(9 * 3600000 + r * 500 + (ri(0, 9) == 0 ? 0 : 0));
             for (int l = 0; l < P.D; l++) {
@@ -61,11 +75,40 @@ int main(int argc, char** argv) {
                 rec[lob_rec_ask_vol(P.D, P.T) + l] = (uint32_t)ri(1, ri(0, 3) ? 30 : 5000);
                 rec[lob_rec_bid_vol(P.D, P.T) + l] = (uint32_t)ri(1, ri(0, 3) ? 30 : 5000);
             }
+            // one float off the grid, unless a neighbouring level then has the same key
+            for (int side = 0; side < 2; side++)
+                for (int l = 0; l < P.D; l++) {
+                    if (ri(0, 9) != 0) continue;
+                    uint32_t* px = rec + (side == 0 ? lob_rec_ask_px(P.D, P.T) : lob_rec_bid_px(P.D, P.T));
+                    const float old = lob_bits_f32(px[l]), moved = nextafterf(old, ri(0, 1) ? 1e9f : 0.0f);
+                    const f64 k = key4((f64)moved);
+                    if ((l > 0 && key4((f64)lob_bits_f32(px[l - 1])) == k) || (l + 1 < P.D && key4((f64)lob_bits_f32(px[l + 1])) == k)) continue;
+                    px[l] = lob_f32_bits(moved);
+                    r_off[r] = true;
+                }
             for (int i = 0; i < P.T; i++)
                 if (ri(0, 1)) {
-                    rec[lob_rec_trade_px(P.D, P.T) + i] = lob_f32_bits((float)((bid_tick + ri(-1, spread + 1)) * tick));
+                    int tt = bid_tick + ri(-1, spread + 1);
+                    if (r > 0 && ri(0, 3) == 0) {   // against the row before: level 3..D, or beyond its last level
+                        const int l = ri(0, 2) ? ri(P.D < 3 ? P.D - 1 : 2, P.D - 1) : P.D + ri(0, 2);
+                        tt = ri(0, 1) ? prev_bid + prev_spread + l : prev_bid - l;
+                        r_deep[r] = true;
+                    }
+                    rec[lob_rec_trade_px(P.D, P.T) + i] = lob_f32_bits((float)(tt * tick));
                     rec[lob_rec_trade_vol(P.D, P.T) + i] = (uint32_t)ri(1, ri(0, 2) ? 40 : 3000);
                 }
+            if (r >= 5 && ri(0, 7) == 0) {   // crossed: the sides swapped and reversed, volumes too
+                uint32_t sw[64];
+                memcpy(sw, rec, sizeof sw);
+                for (int l = 0; l < P.D; l++) {
+                    rec[lob_rec_ask_px(P.D, P.T) + l] = sw[lob_rec_bid_px(P.D, P.T) + P.D - 1 - l];
+                    rec[lob_rec_ask_vol(P.D, P.T) + l] = sw[lob_rec_bid_vol(P.D, P.T) + P.D - 1 - l];
+                    rec[lob_rec_bid_px(P.D, P.T) + l] = sw[lob_rec_ask_px(P.D, P.T) + P.D - 1 - l];
+                    rec[lob_rec_bid_vol(P.D, P.T) + l] = sw[lob_rec_ask_vol(P.D, P.T) + P.D - 1 - l];
+                }
+                r_cross[r] = true;
+            }
+            prev_bid = bid_tick; prev_spread = spread;
             drec_from_abi(rec, P.D, P.T, rows.data() + (size_t)r * P.Wd);
         }
         DevState S;
@@ -126,8 +169,16 @@ int main(int argc, char** argv) {
         row_full_load(c, first, L);
         for (int pass = 0; pass < 3 && first < n_rows - 1; pass++) {
             // the event: rows first..last (mostly one), its trades = slots of rows pf+1..first merged (what the pre-pass stores)
-            const int last = (ri(0, 5) == 0 && first + 1 < n_rows - 1) ? first + 1 : first;
+            int last = first;
+            while ((r_cross[last] || ri(0, 5) == 0) && last + 1 < n_rows - 1) last++;
+            if (r_cross[last]) break;   // (the stream ends inside an invalid state: no event, see the header)
             n_multi += last > first;
+            {
+                bool off = false, sh = false, cr = false, mid = false, deep = false;
+                for (int r = first; r <= last; r++) { off |= r_off[r]; sh |= r_shift[r]; cr |= r_cross[r]; mid |= r_cross[r] && r > first; }
+                for (int r = e1.pf + 1; r <= first; r++) deep |= r >= 0 && r_deep[r];
+                n_offgrid += off; n_shift += sh; n_crossed += cr; n_crossed_mid += mid; n_deep += deep;
+            }
             f64 tp[2]; i64 tv[2];
             load_trades<2>(c, e1.pf + 1, first, tp, tv);
             TrackHead64 t;
@@ -165,6 +216,12 @@ int main(int argc, char** argv) {
             row_full_load(c, first < n_rows - 1 ? first : n_rows - 1, L);
         }
     }
-    printf("pass_diff OK: %ld passes identical (%ld with fills, %ld with queue changes, %ld adverse, %ld multi-row)\n", n_pass, n_fill, n_cancel, n_adverse, n_multi);
+    printf("pass_diff OK: %ld passes identical (%ld with fills, %ld with queue changes, %ld adverse, %ld multi-row; %ld off-grid, %ld shifted, "
+           "%ld crossed, %ld crossed-mid, %ld deep-trades)\n", n_pass, n_fill, n_cancel, n_adverse, n_multi, n_offgrid, n_shift, n_crossed, n_crossed_mid, n_deep);
+    // the sample contains what it is for
+    if (cases >= 10000 && !(n_fill && n_cancel && n_adverse && n_multi && n_offgrid && n_shift && n_crossed && n_crossed_mid && n_deep)) {
+        printf("pass_diff: a counter is zero\n");
+        return 1;
+    }
     return 0;
 }

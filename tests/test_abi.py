@@ -110,6 +110,64 @@ def test_stream_generator_is_deterministic_and_valid():
     assert lib.lob_validate_stream(bad.ctypes.data_as(C.c_void_p), 10, 2, 4, 300) == abi.LOB_EDATA
 
 
+def test_validate_refuses_a_merged_trade_list_beyond_max_trades():
+    """One event's trade list is merged from the rows after the previous event's first row up to its own first row -- rows
+    swallowed by same-timestamp rows and invalid (crossed) states hand their trades on -- and the engine holds it in max_trades
+    slots (LOB_ERR_TRADE_OVERFLOW, a sticky error in the middle of a run).  lob_validate_stream refuses the stream instead:
+    exactly max_trades keys over several rows pass, one more does not, and rows that do not merge may carry what they like."""
+    D, T = 5, 2
+    g = engine.default_gen_params()
+    g.n_events, g.trade_prob_q16, g.move_prob_q16 = 40, 0, 0
+    plain = engine.gen_stream_host(g, D, T, 0, 1)
+    lib = abi.load()
+    otp, otv = 2 + 4 * D, 2 + 4 * D + T
+
+    def check(rec):
+        return lib.lob_validate_stream(rec.ctypes.data_as(C.c_void_p), D, T, 1, 40)
+
+    def trade(rec, row, slot, price, vol=7):
+        rec[0, row, otp + slot] = np.float32(price).view(np.uint32)
+        rec[0, row, otv + slot] = vol
+
+    def cross(rec, row):
+        r = rec[0, row].copy()
+        rec[0, row, 2:2 + D], rec[0, row, 2 + D:2 + 2 * D] = r[2 + 2 * D:2 + 3 * D][::-1], r[2 + 3 * D:2 + 4 * D][::-1]
+        rec[0, row, 2 + 2 * D:2 + 3 * D], rec[0, row, 2 + 3 * D:2 + 4 * D] = r[2:2 + D][::-1], r[2 + D:2 + 2 * D][::-1]
+
+    # rows that do not merge: two keys each, all different
+    a = plain.copy()
+    for row in range(10, 16):
+        trade(a, row, 0, 700.0 + row), trade(a, row, 1, 701.0 + row)
+    assert check(a) == 0
+    # row 20 is crossed: the event that starts at row 20 runs on through row 21, and the event after it merges rows 21 and 22
+    b = plain.copy()
+    cross(b, 20)
+    trade(b, 20, 0, 650.0), trade(b, 20, 1, 651.0)     # (row 20's own trades belong to the event it starts: a list of its own)
+    trade(b, 21, 0, 700.1), trade(b, 22, 0, 700.2)     # two keys over two rows: exactly max_trades
+    assert check(b) == 0
+    trade(b, 21, 1, 700.2)                              # the same key in both rows: still two
+    assert check(b) == 0
+    trade(b, 22, 1, 700.3)                              # a third key
+    assert check(b) == abi.LOB_EDATA
+    msg = lib.lob_last_error()
+    assert msg.startswith(b"book 0 event 22:") and b"events 21..22" in msg and b"max_trades = 2" in msg, msg
+    # the same through a same-timestamp row: row 30 takes row 29's time, so the event of row 29 runs on through row 30
+    c = plain.copy()
+    c[0, 30, 0] = c[0, 29, 0]
+    trade(c, 30, 0, 700.1), trade(c, 30, 1, 700.2), trade(c, 31, 0, 700.2)
+    assert check(c) == 0
+    trade(c, 31, 1, 700.4)
+    assert check(c) == abi.LOB_EDATA and lib.lob_last_error().startswith(b"book 0 event 31:")
+    # a run of crossed rows merges all of them and the row behind
+    d = plain.copy()
+    for row in (10, 11, 12):
+        cross(d, row)
+    trade(d, 11, 0, 700.1), trade(d, 13, 0, 700.2)
+    assert check(d) == 0
+    trade(d, 12, 0, 700.3)
+    assert check(d) == abi.LOB_EDATA and b"events 11..13" in lib.lob_last_error()
+
+
 def test_big_streams_are_validated_by_threads_and_report_the_first_book():
     """Streams of 2^18 records and more are checked by several host threads over contiguous book ranges: the offence reported is
     that of the lowest book (its first event), as the serial scan reports it."""

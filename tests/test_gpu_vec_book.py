@@ -188,6 +188,35 @@ def test_larger_batch_with_one_weight_vector():
     eng.close()
 
 
+def test_hardened_stream_with_crossed_books():
+    """A stream of tests/hard_streams.py (rows that share a timestamp, crossed rows, prices off the grid, jumps): after the reset and
+    every lob_vec_step to the end of the data.  A book whose data ends inside a run of crossed rows is left crossed: those levels too."""
+    from tests import hard_streams as hs
+    B, depth, trades = 65, hs.DEPTH, hs.TRADES
+    rec = hs.batch("all")[0][:B]
+    eng = engine.Engine(make_params(depth, trades), B)
+    eng.load_events(rec)
+    dev = DevBook(B, depth)
+    actions = DevBuf(B, np.int32)
+    vout = abi.VecOut(None, None, None, None, None)
+    rng = np.random.default_rng(77)
+    eng.reset()
+    d = assert_book_equals_dump(eng, dev, depth, "hardened after reset")
+    crossed, steps = 0, 0
+    while (d["terminal"] == 0).any():
+        assert steps < hs.N_EVENTS, "the episode did not end"
+        actions.upload(rng.integers(0, abi.LOB_N_ACTIONS, size=B).astype(np.int32))
+        eng.vec_step(actions.ptr, vout)
+        steps += 1
+        d = assert_book_equals_dump(eng, dev, depth, "hardened vec step %d" % steps)
+        crossed += int((d["ask_px"][:, 0] < d["bid_px"][:, 0]).sum())
+    assert crossed > 0, "crossed books were compared"
+    assert eng.vec_status() == (abi.LOB_OK, 0)
+    actions.free()
+    dev.free()
+    eng.close()
+
+
 # ---- 3. a day library whose longest day is longer than the resident track -------------------------------------------------------------
 
 def test_day_library_in_ring_mode(monkeypatch):

@@ -191,6 +191,40 @@ def test_every_shape_against_the_host_records(B, depth, trades):
     seen.assert_covered({0, 1, 2})
 
 
+def test_hardened_stream_windows():
+    """A stream of tests/hard_streams.py to the end of the data: windows that contain rows sharing a timestamp (their trade slots
+    zeroed), crossed rows and prices off the grid, against the host records as everywhere else."""
+    from tests import hard_streams as hs
+    B, depth, trades = 65, hs.DEPTH, hs.TRADES
+    rec, _, rows = hs.batch("all")
+    rec, same = rec[:B], rows["same_time"][:B]
+    src = Source.per_book(rec)
+    eng = engine.Engine(make_params(depth, trades), B)
+    eng.load_events(rec)
+    devs = [DevHist(B, K, depth, trades) for K in (7, 64)]
+    book = DevBook(B, depth)
+    st = Stepper(eng, 78)
+    seen = Seen()
+    eng.reset()
+    d, steps = run_to_the_end(eng, st, devs, src, depth, trades, "hardened", seen, book)
+    got = devs[0].read(eng)
+    # the last windows of 7 rows: some hold a same-timestamp row, whose time repeats and whose trade slots are empty
+    idx = got["rec"][:, None] - (6 - np.arange(7))[None, :]
+    in_window = np.take_along_axis(same, np.clip(idx, 0, hs.N_EVENTS - 1), axis=1) & (idx >= 0)
+    later = in_window.copy()
+    later[:, 0] = False                       # (slot 0 has no predecessor in the window)
+    assert later.any()
+    bs, ks = np.nonzero(later)
+    np.testing.assert_array_equal(got["time_ms"][bs, ks], got["time_ms"][bs, ks - 1])
+    assert (got["trades"][in_window] == 0).all()
+    assert eng.vec_status() == (abi.LOB_OK, 0)
+    st.free()
+    book.free()
+    for dev in devs:
+        dev.free()
+    eng.close()
+
+
 # ---- 2. stream modes -----------------------------------------------------------------------------------------------------------------
 
 def test_replayed_stream_never_reads_before_the_phase():

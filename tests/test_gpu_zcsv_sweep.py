@@ -22,10 +22,10 @@ from tests.test_oracle_golden import _params_for
 pytestmark = pytest.mark.gpu
 
 
-def run_day(seed, algo, tag):
+def run_day(seed, algo, tag, ulps=False):
     with tempfile.TemporaryDirectory() as td:
         md, tas = os.path.join(td, "md.csv"), os.path.join(td, "tas.csv")
-        craft_csvs(seed, md, tas, ulps=False)   # (prices one float off the grid: pinned on the oracle, not yet run on the GPU)
+        craft_csvs(seed, md, tas, ulps=ulps)    # (ulps: level and trade prices one float off the grid, as the CPU sweep crafts them)
         try:
             rec = engine.convert_csv(md, tas, T_SLOTS)
         except engine.LobError:
@@ -53,9 +53,12 @@ def run_day(seed, algo, tag):
     assert_books_equal(dumps_to_np(eng.get_books()), orc.recs()["book"], tag + " after ClearInventory")
     np.testing.assert_array_equal(eng.theta(0), orc.theta(0), err_msg=tag)
     dry = bool((rec[0, :, 1] & abi.EVT_FLAG_TAS_DRY).any())
+    px = rec[0, :, 2:22].view(np.float32)     # the five ask and five bid prices and, between them, the ask volumes (never off-grid floats)
+    px = np.concatenate([px[:, :5], px[:, 10:15]], axis=1)
+    off_grid = bool((px != (np.rint(px.astype(np.float64) * 10.0) / 10.0).astype(np.float32)).any())
     eng.close()
     orc.close()
-    return n, dry
+    return n, dry, off_grid
 
 
 def test_engine_on_crafted_csv_days():
@@ -69,6 +72,23 @@ def test_engine_on_crafted_csv_days():
         failed_init += out[0] == 0
     # the sample really contains what it is for
     assert steps > 500 and dry_days >= 3 and failed_init >= 1
+
+
+def test_engine_on_crafted_csv_days_with_prices_off_the_grid():
+    """The same days as tests/test_convert_ref_sweep.py crafts them for the oracle against the reference: level and trade prices
+    one float off the grid (mostly the same 1e-4 key with other bits, now and then the next key; trades at one key under
+    different bits merged under the first-seen price)."""
+    steps, dry_days, failed_init, off_grid_days = 0, 0, 0, 0
+    for k in range(24):
+        out = run_day(91000 + k, "sarsa" if k % 2 else "q_learn", "csv day %d, prices off the grid" % k, ulps=True)
+        if out is None:
+            continue
+        steps += out[0]
+        dry_days += out[1]
+        failed_init += out[0] == 0
+        off_grid_days += out[2]
+    # the sample really contains what it is for: the converted records hold level prices that are not the grid's floats
+    assert steps > 500 and dry_days >= 3 and failed_init >= 1 and off_grid_days >= 12
 
 
 @pytest.mark.parametrize("fuse", [0, 1])

@@ -7,6 +7,7 @@ general pass (next_state + step_event, the restatement pinned by the oracle sinc
 fast pass (pass_fast, what env_kernel<., 2, .> runs) must leave bit-identical EnvR and StepAgg.  The GPU suite
 then compares the whole kernel with the oracle; this test localises a discrepancy to the pass and runs here."""
 import os
+import re
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,6 +20,10 @@ def test_fast_pass_equals_general_pass(tmp_path):
     out = subprocess.run([exe, os.environ.get("LOB_PASS_DIFF_CASES", "300000")], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout[-2000:]
     assert "pass_diff OK" in out.stdout
+    # the sample contains what it is for: fills, queue changes, adverse selection, multi-row events, and the rows vendor files
+    # make -- prices off the grid, rows shifted by several ticks, crossed rows (also in the middle of an event), deep trades
+    counts = [int(n) for n in re.findall(r"(\d+) (?:with|adverse|multi|off|shifted|crossed|deep)", out.stdout)]
+    assert len(counts) == 9 and min(counts) > 0, out.stdout
 
 
 def test_exp_restatement_equals_libm(tmp_path):
