@@ -228,6 +228,8 @@ struct lob_engine {
     int timing_period = 1;  // kernels of every n-th step are timed (two event records per launch are not free: 9 % at n = 1)
     std::map<std::string, KTimer> timers;
     std::vector<hipEvent_t> event_pool;
+    // lob_debug_launches (below, beside lob_debug_flow): launches of kernels that share a timer name
+    int64_t launched[6] = {0, 0, 0, 0, 0, 0};
 };
 
 namespace {
@@ -1338,7 +1340,8 @@ int lob_reset(lob_engine* e) {
     }
     {
         TimedLaunch t(e, "reset_kernel", nullptr, true);
-        lobk_reset(e->stream, e->sw.reset_lanes, e->P.T <= 2, e->sw.prepass_roles, (const DevParams*)e->P_dev, e->S);
+        // (a ring: never the two-wave form, which cannot follow a warm-up beyond the ring's first fill -- lob_kernels.h reset2_kernel)
+        lobk_reset(e->stream, e->sw.reset_lanes, e->P.T <= 2, e->sw.prepass_roles && !e->chunked, (const DevParams*)e->P_dev, e->S);
     }
     HIPCHK(hipGetLastError());
     e->was_reset = true;
@@ -1947,8 +1950,8 @@ static int act_half(lob_engine* e, const StepPlan& sp, const StepGroup& gr, int 
         const EnvFuse F1{nullptr, nullptr, sp.lpar, sid - 1, sp.ver}, F2{act_list, act_n, sp.lpar, sid - 1, sp.ver};
         {
             TimedLaunch t(e, "env_kernel", st);
-            if (e->plan.env_step) lobk_env_step(st, sp.inline_general, dq, e->plan.half_waves, e->plan.env16, Pd, e->S, nb, sid, sp.par, F1, rnd);
-            else lobk_env_mode(st, t2, 1, Pd, e->S, nb, sid, sp.par, F1);
+            if (e->plan.env_step) e->launched[lobk_env_step(st, sp.inline_general, dq, e->plan.half_waves, e->plan.env16, Pd, e->S, nb, sid, sp.par, F1, rnd)]++;
+            else { e->launched[2]++; lobk_env_mode(st, t2, 1, Pd, e->S, nb, sid, sp.par, F1); }
         }
         if (!sp.inline_general) {
             {
@@ -2035,10 +2038,14 @@ static int learn_half(lob_engine* e, const StepPlan& sp, const StepGroup& gr) {
         if (pl.q_lanes) {
             const bool pair = pl.q_pair;
             if (pair && !e->S.theta_nzm) { lob_set_error("learn_q_pair_kernel: no action-mask table (theta_nzm)"); return LOB_ESTATE; }
+            e->launched[pair ? 3 : 4]++;
             const int gq = pair ? std::min(LOB_QP_OCC * e->n_cus, (nb + LOB_QP_BOOKS - 1) / LOB_QP_BOOKS) : std::min(e->n_cus, (nb + LOB_QL_BLOCK - 1) / LOB_QL_BLOCK);
             const size_t lds = pair ? qpair_lds_bytes(e->P.cwords4) : qlane_lds_bytes(e->P.cwords4);
             lobk_learn_q(st, pair, algo, e->P.V == 8, pl.fuse, gq, lds, (const DevParams*)e->P_dev, e->S, rnd, lpar, sp.ver, sid, acc_fuse);
-        } else lobk_learn_q_fast(st, algo, gr.gf, fast_lds_bytes(e->P.cwords4, LOB_FAST_NB, false), (const DevParams*)e->P_dev, e->S, rnd, lpar, sp.ver);
+        } else {
+            e->launched[5]++;
+            lobk_learn_q_fast(st, algo, gr.gf, fast_lds_bytes(e->P.cwords4, LOB_FAST_NB, false), (const DevParams*)e->P_dev, e->S, rnd, lpar, sp.ver);
+        }
     }
     if (!sp.rest_merged) {   // (rest_merged: trace_rest_kernel serves the books handed back too, behind the lane trace kernel)
         // The books the lane kernels hand back (a list that is empty in most steps, a handful of books in the others).
@@ -2802,6 +2809,16 @@ extern "C" int lob_debug_fastpath(lob_engine* e, int64_t* out, int32_t n_out) {
 extern "C" int lob_debug_flow(lob_engine* e, int64_t out[8]) {
     if (!e || !out) return LOB_EINVAL;
     for (int i = 0; i < 8; i++) out[i] = e->flow[i];
+    return LOB_OK;
+}
+
+// Diagnostics (not part of include/lob_engine.h): launches since lob_create of kernels that share a timer name ("env_kernel",
+// "learn_kernel") -- [0] env_step_kernel, [1] env_step16_kernel (which of the two: lobk_env_step says), [2] the fused
+// env_kernel<., ., 1>, [3] learn_q_pair_kernel, [4] learn_q_lane_kernel, [5] learn_q_fast_kernel.  Host counters; the tests use
+// them to show which kernel a case has compared with the oracle.
+extern "C" int lob_debug_launches(lob_engine* e, int64_t out[6]) {
+    if (!e || !out) return LOB_EINVAL;
+    for (int i = 0; i < 6; i++) out[i] = e->launched[i];
     return LOB_OK;
 }
 

@@ -196,7 +196,22 @@ __global__ void __launch_bounds__(RB) reset_kernel(const DevParams* __restrict__
         // the whole stream when its track is resident, else the first ring-full (prepass_extend_kernel goes on from there)
         PrepState st;
         prepass_begin(c, st, M);
-        prepass_run<TM>(c, st, M, S.track_mask == 0x7fffffff ? 0x7fffffff : S.track_len - LOB_TRACK_MARGIN, true);
+        // A ring whose first fill ends before Initialise's warm-up does (look-backs of 256 events on a ring of 256; windows that
+        // only trades feed, on a quiet market, on any ring): out of data it is not.  The pre-pass then goes on event by event
+        // until the windows are full -- only entries k_warm - 2 .. are ever read, the older ones may be overwritten -- and fills
+        // the ring from there as prepass_extend_kernel would from the episode's first cursor: the first refill is
+        // LOB_TRACK_REFILL steps away.  (One call site in a loop: the pre-pass is 50 KB of code.  A book whose warm-up ends
+        // inside the first fill leaves the loop after one round, as before.)
+        const bool ring = S.track_mask != 0x7fffffff;
+        const int k_first = ring ? S.track_len - LOB_TRACK_MARGIN : 0x7fffffff;
+        int k_stop = k_first;
+        for (;;) {
+            prepass_run<TM>(c, st, M, k_stop, true);
+            if (!ring || M.complete) break;
+            if (M.k_warm < 0) { k_stop++; continue; }
+            if (M.k_warm <= k_first || k_stop >= M.k_warm + k_first) break;
+            k_stop = M.k_warm + k_first;
+        }
         S.meta[b] = M;
         S.prep[b] = st;
     }
@@ -288,6 +303,8 @@ __global__ void __launch_bounds__(128, 2) reset2_kernel(const DevParams* __restr
         st.ewma_up = S.ewma_up[b]; st.ewma_down = S.ewma_down[b]; st.tp_val = S.tp_val[b];
         st.k = 0;
     }
+    // (NOT reset_kernel's loop past the ring's first fill: the two roles meet at barriers and cannot go on book by book, so a
+    // warm-up that outlasts the first fill would read as out of data here.  lob_reset gives a ring to the one-wave kernel.)
     prepass_run2<TM>(c, st, M, S.track_mask == 0x7fffffff ? 0x7fffffff : S.track_len - LOB_TRACK_MARGIN, on, role, xch, lane);
     // the window role's last words (ewma, target price) belong in the resumable state the book role's lanes write
     f64* hand = reinterpret_cast<f64*>(&xch[0]);

@@ -449,6 +449,15 @@ class Engine:
                 "act_inline_general": int(c[4]), "act_work_list_dense": int(c[5]), "act_work_list_other": int(c[6]),
                 "dense_sums": int(c[7])}
 
+    def launches(self):
+        """lob_debug_launches (a diagnostic export): launches since lob_create of the kernels that share a timer name."""
+        c = np.zeros(6, np.int64)
+        fn = self.lib.lob_debug_launches
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p]
+        self._check(fn(self.h, _ptr(c)))
+        return {"env_step_kernel": int(c[0]), "env_step16_kernel": int(c[1]), "env_kernel_fused": int(c[2]),
+                "learn_q_pair_kernel": int(c[3]), "learn_q_lane_kernel": int(c[4]), "learn_q_fast_kernel": int(c[5])}
+
     def hint_stats(self):
         """lob_debug_hint (a diagnostic export): learner steps that read the learn kernels' hand-back count, and of those the steps
         whose count had not arrived in time and that went by 0 instead (their act / update path was chosen by the host's timing)."""

@@ -245,10 +245,10 @@ def test_traffic_table_is_what_the_committed_counter_passes_give(tmp_path):
 
 
 def test_diagnostic_exports_are_outside_the_header():
-    """The lob_debug_* exports (Engine.flow_stats, hint_stats, fastpath_stats, deferred_generations; the light-book count) are
+    """The lob_debug_* exports (Engine.flow_stats, hint_stats, fastpath_stats, deferred_generations, launches; the light-book count) are
     diagnostics the tests read: exported by the library, declared nowhere in include/lob_engine.h or its ctypes mirror."""
     lib = abi.load()
     declared = set(header_functions()) | set(lib._declared)
-    for n in ("lob_debug_flow", "lob_debug_hint", "lob_debug_fastpath", "lob_debug_deferred", "lob_debug_light"):
+    for n in ("lob_debug_flow", "lob_debug_hint", "lob_debug_fastpath", "lob_debug_deferred", "lob_debug_light", "lob_debug_launches"):
         assert hasattr(lib, n), "liblob_engine.so does not export %s" % n
         assert n not in declared, n

@@ -43,6 +43,22 @@ def test_exp_restatement_equals_libm(tmp_path):
             assert line.strip().rstrip("\\").rstrip().rstrip(",") in hdr
 
 
+def test_expf_restatement_equals_libm(tmp_path):
+    """Base::getReward's mm_exp measure calls std::exp(float); the fused env step restates glibc's expf on the device (lob_env.h
+    expf_glibc, inside get_reward).  tests/host_env/expf_diff.cpp compiles that function from the device header and holds it
+    against this libm's expf bit for bit: the whole MM_EXP argument range the sweeps draw (pos_weight <= 0.2 times positions up
+    to 10 000, a float product that crosses the overflow threshold), the over- and underflow thresholds and their neighbours,
+    +-0, +-inf, NaNs, and 10^7 random bit patterns."""
+    exe = str(tmp_path / "expf_diff")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-mfma", "-ffp-contract=off", "-I" + os.path.join(ROOT, "tests", "host_env", "shim"),
+                           "-o", exe, os.path.join(ROOT, "tests", "host_env", "expf_diff.cpp")])
+    out = subprocess.run([exe, os.environ.get("LOB_EXPF_CASES", "10000000")], capture_output=True, text=True)
+    assert out.returncode == 0 and "mismatches 0" in out.stdout and "expf_diff OK" in out.stdout, out.stdout[-1500:]
+    # the sample contains what it is for: finite results, overflow inside the MM_EXP range, underflow to zero, subnormals, NaNs
+    m = re.search(r"checked (\d+) \((\d+) of the MM_EXP range, (\d+) of them \+inf\); results: (\d+) inf, (\d+) zero, (\d+) subnormal, (\d+) NaN", out.stdout)
+    assert m and int(m.group(1)) > 30000000 and all(int(m.group(i)) > 0 for i in range(2, 8)), out.stdout
+
+
 def test_same_cell_arithmetic_equals_tile_coord_and_implies_same_index(tmp_path):
     """trace_lane_kernel decides which tiles an old trace generation loses to a new state from the quantised coordinates
     alone (lob_tiles.h tile_same_cell_mask).  tests/host_env/cell_diff.cpp, compiled from the device header: the mask equals
