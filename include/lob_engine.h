@@ -559,6 +559,50 @@ typedef struct lob_vec_act_out {   /* DEVICE pointers on the engine's GPU; any m
 int lob_vec_act(lob_engine* e, int32_t mode, const lob_vec_act_out* out);
 int lob_vec_q(lob_engine* e, const float* dev_vars, int32_t n, double* dev_q);
 
+/* ---- vector-env interface: the tile features of a state and external weight updates, on the device ---
+ * The other direction of lob_vec_act / lob_vec_q: a learner on the same GPU sees the representation the engine's agent is built on
+ * -- the CMAC tiles of State::populateFeatures (src/rl/state.cpp:56-63, src/rl/tiles.cpp:31-75) -- and lands any target it has
+ * computed in the engine's weights as a semi-gradient step on the tiles of (state, action).  theta keeps its format: lob_theta_get,
+ * lob_run and the reference's own agent read it, and lob_vec_act, lob_eval_step and lob_td_step use the new weights in the next call.
+ *   Rows, in both calls (lob_vec_act / lob_vec_q's rule): dev_vars == NULL: the books' latest getState() -- the row lob_vec_step
+ * wrote to obs --, n must be n_books and a lob_reset must have happened; else n >= 1 free-standing states, f32 [n][n_vars] in device
+ * memory on the engine's GPU, and no lob_reset is needed.
+ *   Tile positions: p = 32 g + j is tiling j of tile group g (0: the first three variables, 1: the others, 2: all) -- the order of
+ * lob_features' last axis; LOB_N_TILES = 96 of them.
+ *   lob_vec_terms: host_out[g * LOB_N_ACTIONS + a] = the action term of group g, reduced mod memory_size.  Host-only: it touches no
+ * device and never fails for a valid engine and pointer.
+ *   lob_vec_features: out->sums[s][p] = the action-independent hash sum of position p, reduced mod M = memory_size.  ONE contract
+ * for all nine actions:
+ *         (sums[s][p] + terms[g][a]) mod M   ==   lob_features' [s][a][p], bit for bit
+ * -- 384 bytes per state where the cube takes 3 456.  0 <= sums < M <= 2^31 - 1 and 0 <= terms < M: DO THE ADDITION IN 64 BITS (or
+ * unsigned 32), a signed 32-bit sum can overflow.  out->idx[s][p] = that index for a = dev_actions[s]; a row whose action is outside
+ * [0, LOB_N_ACTIONS) gets -1 in all 96 places.  A NULL member is skipped (the buffer is not touched); both NULL: LOB_OK, nothing is
+ * launched.  Nothing of the engine's state changes.
+ *   lob_vec_update: for every row s whose action is in range and whose dev_step[s] != 0.0, dev_step[s] is added to each of the 96
+ * weights of (row s, dev_actions[s]).  The increment is the caller's whole per-tile amount: the engine applies no alpha and does not
+ * divide by the number of tilings (the learner's own step adds alpha * delta / 32 per tile).  Target: shared theta: the one vector;
+ * private theta: book s's vector in the books' form, book 0's for free-standing rows (the vector lob_vec_q reads); second = 1: theta_b
+ * -- LOB_EINVAL unless the algorithm is LOB_ALGO_DOUBLE_Q.  The action is looked at first: a row whose action is out of range is
+ * skipped and counted in the word lob_vec_status reports and clears (no error flag is raised); then a row whose step is exactly 0.0
+ * writes and marks nothing.  A non-finite step is the caller's business and is added as it is.  The additions are f64 atomics in no
+ * fixed order, as the learner's own: a weight that several rows share receives its increments in an order that can differ from run
+ * to run (exact whenever every partial sum is).  The written-weights maps, the verdicts and the memo records are kept as
+ * lob_delta_apply keeps them; the multi-GPU base is NOT moved -- an external update is a local change and the next exchange carries
+ * it.  Traces, rho, the random counters and the learner's record of the last step are not touched.
+ *   Both device calls are enqueued on the engine's stream (lob_stream) and return at once: no host read, no allocation, no copy and
+ * no synchronisation.  LOB_EINVAL, with a message naming the call: a NULL engine, a NULL out / dev_actions / dev_step where required
+ * (idx wanted without dev_actions), n < 1, n != n_books in the books' form, second outside 0 / 1.  LOB_ESTATE: between
+ * lob_td_step_begin and lob_td_step_end, and the books' form before the first lob_reset.  Allowed after lob_snapshot_restore: neither
+ * call reads the learner's memory of the last transition. */
+#define LOB_N_TILES 96            /* 3 groups x 32 tilings, the order of lob_features' last axis */
+typedef struct lob_vec_feat_out { /* DEVICE pointers on the engine's GPU; NULL = not wanted */
+    int32_t* sums;                /* [n][LOB_N_TILES] */
+    int32_t* idx;                 /* [n][LOB_N_TILES]; needs dev_actions */
+} lob_vec_feat_out;
+int lob_vec_terms(lob_engine* e, int32_t host_out[27]);   /* [group][action], reduced mod memory_size */
+int lob_vec_features(lob_engine* e, const float* dev_vars, int32_t n, const int32_t* dev_actions, const lob_vec_feat_out* out);
+int lob_vec_update(lob_engine* e, const float* dev_vars, int32_t n, const int32_t* dev_actions, const double* dev_step, int32_t second);
+
 /* ---- episode statistics of the whole batch ---------------------------------
  * What the reference logs about ONE environment after an episode -- the `training_log` row of Runner::RunEpisode
  * (src/experiment/serial.cpp:81-88: getEpisodeReward, getEpisodePnL, total_ticks), Base::writeStats and getTotalTransactions

@@ -176,6 +176,15 @@ class VecActOut(C.Structure):
     _fields_ = [("action", C.c_void_p), ("q", C.c_void_p)]
 
 
+# lob_vec_features / lob_vec_update: tile positions per state (LOB_N_TILES: 3 groups x 32 tilings, lob_features' last axis)
+N_TILES = 96
+
+
+class VecFeatOut(C.Structure):
+    """lob_vec_feat_out: where lob_vec_features writes, two DEVICE addresses (0 = not wanted)."""
+    _fields_ = [("sums", C.c_void_p), ("idx", C.c_void_p)]
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LOB_ENGINE_LIB: an experiment build of the same library (tools/exp_prof.py, tools/exp_variants.sh)
 LIB_PATH = os.environ.get("LOB_ENGINE_LIB") or os.path.join(_HERE, "csrc", "liblob_engine.so")
@@ -248,6 +257,9 @@ def load():
         "lob_vec_history": (C.c_int, [vp, C.c_int32, P(VecHistOut)]),
         "lob_vec_act": (C.c_int, [vp, C.c_int32, P(VecActOut)]),
         "lob_vec_q": (C.c_int, [vp, vp, C.c_int32, vp]),
+        "lob_vec_terms": (C.c_int, [vp, P(C.c_int32)]),
+        "lob_vec_features": (C.c_int, [vp, vp, C.c_int32, vp, P(VecFeatOut)]),
+        "lob_vec_update": (C.c_int, [vp, vp, C.c_int32, vp, vp, C.c_int32]),
         "lob_snapshot_save": (C.c_int, [vp, C.c_int32, C.c_void_p]),
         "lob_snapshot_restore": (C.c_int, [vp, C.c_int32, C.c_void_p]),
         "lob_snapshot_free": (C.c_int, [vp, C.c_int32]),

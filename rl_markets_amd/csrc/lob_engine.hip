@@ -199,6 +199,9 @@ struct lob_engine {
     Track* track_dev = nullptr;
     i32* actions_dev = nullptr;
     u64* vec_bad = nullptr;     // lob_vec_step: actions out of range since the last lob_vec_status / lob_reset (one device word)
+    i32* vec_upd_tag = nullptr; // lob_vec_update: the number of the last launch that wrote a weight (one device word; lob_launch.h VecFeatSrc)
+    i32 vec_upd_launch = 0;     // ... and the number of the last launch (never 0 once used)
+    uint32_t vec_terms[27] = {0};   // lob_vec_terms: the 27 action terms mod M, as uploaded behind the hash table
     i64* cnt_sum = nullptr;     // the striped device counters added up (read_counters)
     lob_book_dump* dump_dev = nullptr;
     int dump_cap = 0;
@@ -715,6 +718,7 @@ int lob_create(const lob_params* p, int32_t n_books, int32_t device, lob_engine*
     S.nzd_terms = e->rnd_dev ? e->rnd_dev + 2048 + LOB_N_ACTIONS : nullptr;  // term[1][.], term[2][.] (filled below)
     alloc(&e->actions_dev, B); alloc(&e->P_dev, 1); alloc(&e->S_dev, 1);
     alloc(&e->vec_bad, 1);
+    alloc(&e->vec_upd_tag, 1);
     if (rc == LOB_OK && hipMemsetAsync(e->vec_bad, 0, sizeof(u64), e->stream) != hipSuccess) rc = LOB_EHIP;
     if (rc == LOB_OK) { S.self = e->S_dev; memset(&e->S_pushed, 0xff, sizeof(DevState)); }
     if (rc == LOB_OK) rc = push_params(e);
@@ -741,6 +745,7 @@ int lob_create(const lob_params* p, int32_t n_books, int32_t device, lob_engine*
             for (int a = 0; a < LOB_N_ACTIONS; a++)
                 terms[g * LOB_N_ACTIONS + a] = (uint32_t)((uint64_t)raw[((g * LOB_N_ACTIONS + a) + 449 * (nf + 1)) & 2047] % (uint64_t)P.M);
         }
+        memcpy(e->vec_terms, terms, sizeof e->vec_terms);
         for (int k = 0; k < 2048; k++) rnd[k] = (uint32_t)((uint64_t)rnd[k] % (uint64_t)P.M);  // the device only ever sums the table mod M
         HIPCHK_E(hipMemcpyAsync(e->rnd_dev, rnd, sizeof rnd, hipMemcpyHostToDevice, e->stream));
         HIPCHK_E(hipStreamSynchronize(e->stream));
@@ -1575,6 +1580,76 @@ int lob_vec_q(lob_engine* e, const float* dev_vars, int32_t n, double* dev_q) {
         TimedLaunch t(e, "vec_q_kernel", nullptr, true);
         lobk_vec_act(e->stream, false, e->n_cus, LOB_PS(e), (const uint32_t*)e->rnd_dev, a);
     }
+    HIPCHK(hipGetLastError());
+    return LOB_OK;
+}
+
+// ---- tile features and external weight updates (include/lob_engine.h lob_vec_features / lob_vec_update; lob_tu_vecfeat.hip) ----
+int lob_vec_terms(lob_engine* e, int32_t host_out[27]) {
+    if (!e || !host_out) { lob_set_error("lob_vec_terms: NULL argument"); return LOB_EINVAL; }
+    for (int i = 0; i < 27; i++) host_out[i] = (int32_t)e->vec_terms[i];   // (< M <= 2^31 - 1)
+    return LOB_OK;
+}
+// The argument checks the two device calls share: the rows' rule of lob_vec_act / lob_vec_q
+static int vec_feat_entry(lob_engine* e, const float* dev_vars, int32_t n, const char* who) {
+    if (!e) { lob_set_error(std::string(who) + ": NULL engine"); return LOB_EINVAL; }
+    if (n < 1) { lob_set_error(std::string(who) + ": n = " + std::to_string(n) + " (at least one row)"); return LOB_EINVAL; }
+    if (!dev_vars && n != e->B) { lob_set_error(std::string(who) + ": n = " + std::to_string(n) + " but dev_vars == NULL means the engine's " + std::to_string(e->B) + " books"); return LOB_EINVAL; }
+    int rc = not_mid_step(e, who);
+    if (rc) return rc;
+    return dev_vars ? LOB_OK : need_reset(e, who);
+}
+// The hash sums / tile indices of n states into the caller's device buffers: one launch on the engine's stream, nothing changed.
+int lob_vec_features(lob_engine* e, const float* dev_vars, int32_t n, const int32_t* dev_actions, const lob_vec_feat_out* out) {
+    if (e && !out) { lob_set_error("lob_vec_features: NULL out"); return LOB_EINVAL; }
+    if (e && out->idx && !dev_actions) { lob_set_error("lob_vec_features: idx wanted without dev_actions"); return LOB_EINVAL; }
+    int rc = vec_feat_entry(e, dev_vars, n, "lob_vec_features");
+    if (rc) return rc;
+    if (!out->sums && !out->idx) return LOB_OK;
+    HIPCHK(hipSetDevice(e->device));
+    VecFeatSrc a;
+    memset(&a, 0, sizeof a);
+    a.rows = dev_vars; a.actions = out->idx ? dev_actions : nullptr; a.n = n;
+    a.sums = out->sums; a.idx = out->idx;
+    {
+        TimedLaunch t(e, "vec_features_kernel", nullptr, true);
+        lobk_vec_feat(e->stream, e->n_cus, LOB_PS(e), (const uint32_t*)e->rnd_dev, a);
+    }
+    HIPCHK(hipGetLastError());
+    return LOB_OK;
+}
+// theta[tile] += step over the tiles of (row, action), from outside a step.  On the device the kernel keeps the maps as
+// delta_apply_kernel does; here the host does what lob_theta_set does around its kernels -- except for the multi-GPU base, which
+// stays: the update is a local change and the next exchange carries it.
+int lob_vec_update(lob_engine* e, const float* dev_vars, int32_t n, const int32_t* dev_actions, const double* dev_step, int32_t second) {
+    if (e && (!dev_actions || !dev_step)) { lob_set_error("lob_vec_update: NULL argument"); return LOB_EINVAL; }
+    if (e && second != 0 && second != 1) { lob_set_error("lob_vec_update: second = " + std::to_string(second) + " is neither 0 nor 1"); return LOB_EINVAL; }
+    if (e && second && e->P.algo != LOB_ALGO_DOUBLE_Q) { lob_set_error("lob_vec_update: second = 1 needs LOB_ALGO_DOUBLE_Q (there is no theta_b)"); return LOB_EINVAL; }
+    int rc = vec_feat_entry(e, dev_vars, n, "lob_vec_update");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    VecFeatSrc a;
+    memset(&a, 0, sizeof a);
+    a.rows = dev_vars; a.actions = dev_actions; a.n = n; a.step = dev_step;
+    a.theta = second ? e->S.theta_b : e->S.theta;
+    a.nz = second ? e->S.theta_b_nz : e->S.theta_nz;
+    if (e->P.memo) {   // (double Q: one set of maps for both vectors)
+        a.nzx = e->S.theta_nzx; a.nzc = e->S.theta_nzc; a.nzd = e->S.theta_nzd; a.nzm = e->S.theta_nzm; a.nzd_terms = e->S.nzd_terms;
+        a.cshift = e->P.cshift;
+    }
+    a.nz_epoch = e->S.nz_epoch;
+    a.tag = e->vec_upd_tag;
+    a.launch = e->vec_upd_launch = e->vec_upd_launch == INT32_MAX ? 1 : e->vec_upd_launch + 1;
+    a.n_bad = e->vec_bad;
+    e->theta_ver++;  // memo records computed under the old weights are void
+    e->hits_ok = false;
+    e->hint_step = 0;  // (... and so is what the learn kernels handed back under them)
+    e->rest_recent = 0;
+    {
+        TimedLaunch t(e, "vec_update_kernel", nullptr, true);
+        lobk_vec_feat(e->stream, e->n_cus, LOB_PS(e), (const uint32_t*)e->rnd_dev, a);
+    }
+    if (e->P.memo && e->was_reset) launch_memo(e, e->last_par, 1);  // the current triples under the new weights: the next act stays on the fast path
     HIPCHK(hipGetLastError());
     return LOB_OK;
 }

@@ -1,7 +1,7 @@
-// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is eleven
+// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is twelve
 // .hip files built in parallel: lob_engine.hip -- the C ABI's host side and the update / memo / trace kernels --, lob_tu_env.hip,
 // lob_tu_prepass.hip, lob_tu_learn.hip, lob_tu_stats.hip, lob_tu_steplog.hip, lob_tu_vec.hip, lob_tu_vecbook.hip, lob_tu_vechist.hip, lob_tu_snapshot.hip,
-// lob_tu_vecact.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
+// lob_tu_vecact.hip, lob_tu_vecfeat.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
 // lob_engine.hip used when it held the launches itself.  Kernels measured and lost (NOTES.md "Round 4") are only compiled with
 // -DLOB_EXPERIMENTS (tools/exp_variants.sh); a product build answers LOB_EXPERIMENTS-only requests with the product kernel.
 #ifndef LOB_LAUNCH_H
@@ -188,6 +188,36 @@ struct VecActSrc {
 // vec_act_kernel<books, dq>: a persistent grid of at most LOB_VECACT_MAX_BLOCKS blocks, sized from the compute units (`n_cus`); `dq`: the
 // double agents' second weight vector (the books' form only: a.rows null)
 void lobk_vec_act(hipStream_t st, bool dq, int n_cus, const DevParams* Pd, const DevState* Sd, const uint32_t* rnd, const VecActSrc& a);
+
+// ---- lob_tu_vecfeat.hip ----
+// What lob_vec_features / lob_vec_update (include/lob_engine.h) read and write beyond the parameters and the state, which
+// vec_feat_kernel takes by pointer (lob_state.h LOB_PS_ARGS): the caller's device buffers and, for an update, the target weight vector
+// with every map delta_apply_kernel keeps for it -- filled in by the host in both forms, so that the free-standing form reads nothing
+// of the state (valid before the first lob_reset, when the state's device-resident copy has not been uploaded yet) and the books'
+// form only the rows.
+#define LOB_VECFEAT_MAX_BLOCKS 2048
+struct VecFeatSrc {
+    const f32* rows;       // free-standing states [n][V] (null: the books' latest getState(), slot 2 of DevState::vars)
+    const i32* actions;    // [n] (null: no action; features without idx only)
+    i32 n;                 // states: the books, or the caller's rows
+    i32* sums;             // features: [n][LOB_N_TILES] (null: not wanted)
+    i32* idx;              // features: [n][LOB_N_TILES] (null: not wanted)
+    const f64* step;       // update: [n] per-tile increments (null: a features launch)
+    f64* theta;            // update: the target vector -- theta or theta_b; book 0's under private theta (the books' form adds s * M)
+    uint32_t* nz;          // ... its "ever written" map (the books' form adds s * LOB_NZ_NWORDS(M) under private theta)
+    uint32_t* nzx;         // ... the memo path's exact map (null: not on the memo path), its coarse image, the maps folded over the
+    uint32_t* nzc;         //     actions and their terms: delta_apply_kernel's arguments
+    uint32_t* nzd;
+    uint32_t* nzm;
+    const uint32_t* nzd_terms;
+    i32 cshift;
+    i32* nz_epoch;         // bumped once by a launch that writes anything
+    i32* tag;              // ... [1] the number of the last launch that did (`launch`: this one's, never 0)
+    i32 launch;
+    u64* n_bad;            // rows skipped for an action out of range (the word lob_vec_status reports and clears)
+};
+// vec_feat_kernel<books, update>: a persistent grid of at most LOB_VECFEAT_MAX_BLOCKS blocks, sized from the compute units (`n_cus`)
+void lobk_vec_feat(hipStream_t st, int n_cus, const DevParams* Pd, const DevState* Sd, const uint32_t* rnd, const VecFeatSrc& a);
 
 // ---- lob_tu_learn.hip ----
 // learn_q_pair_kernel / learn_q_lane_kernel<algo, vt, tr>: vt = 8 when the state has eight variables (else 0)

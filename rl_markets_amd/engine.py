@@ -314,6 +314,27 @@ class Engine:
         enqueued on the engine's stream."""
         self._check(self.lib.lob_vec_q(self.h, C.c_void_p(vars_ptr), int(n), C.c_void_p(q_ptr)))
 
+    def vec_terms(self):
+        """lob_vec_terms: the 27 action terms [group][action] of the tile hash, reduced mod memory_size -- a list of three lists of
+        nine ints.  (sums + term) mod M is the tile index (vec_features); host-only, no device is touched."""
+        buf = (C.c_int32 * 27)()
+        self._check(self.lib.lob_vec_terms(self.h, buf))
+        return [list(buf[g * abi.LOB_N_ACTIONS:(g + 1) * abi.LOB_N_ACTIONS]) for g in range(3)]
+
+    def vec_features(self, vars_ptr, n, actions_ptr, out):
+        """lob_vec_features: the 96 action-independent hash sums of n states' tiles (out.sums, int32 [n, 96]) and the tile indices
+        of the action at `actions_ptr` (int32 [n]) per state (out.idx, int32 [n, 96]; -1 for an action out of range) into the device
+        buffers of `out` (abi.VecFeatOut; 0 = not wanted).  `vars_ptr`: f32 [n, n_vars] in device memory, or None: the books' latest
+        observation (n = n_books).  Enqueued on the engine's stream."""
+        self._check(self.lib.lob_vec_features(self.h, C.c_void_p(vars_ptr), int(n), C.c_void_p(actions_ptr), C.byref(out)))
+
+    def vec_update(self, vars_ptr, n, actions_ptr, step_ptr, second=False):
+        """lob_vec_update: adds step[s] (f64 [n] at `step_ptr`) to each of the 96 weights of (row s, action[s]) -- the caller's whole
+        per-tile amount, no alpha, no division by the tilings.  Rows as vec_features; private theta: book s's vector (the books' form)
+        or book 0's (free-standing rows); second: theta_b (double Q).  Rows with an action out of range are skipped and counted
+        (vec_status).  Enqueued on the engine's stream."""
+        self._check(self.lib.lob_vec_update(self.h, C.c_void_p(vars_ptr), int(n), C.c_void_p(actions_ptr), C.c_void_p(step_ptr), 1 if second else 0))
+
     def snapshot_save(self, slot, mask_ptr=None):
         """lob_snapshot_save: the environment state of the books selected by the DEVICE mask at address `mask_ptr` (uint8 [B],
         nonzero selects; None: every book, which (re)starts the slot) into snapshot slot `slot` (0 .. abi.MAX_SNAPSHOTS - 1);

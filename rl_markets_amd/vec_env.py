@@ -40,6 +40,21 @@ f64 [B, 9].  env.step(env.act()) is one agent step of the engine's greedy policy
 restore() has put back.  q_values(vars) evaluates the same weights on any f32 [n, V] tensor of states (lob_vec_q).  A VecEnv that
 never calls act() allocates and launches nothing for it.
 
+features() / tile_index() / update() open the agent's representation and its weights to a learner in torch (lob_vec_features,
+lob_vec_update).  features() refreshes and returns .feat_sums, int32 [B, 96]: the action-independent hash sums of the 96 tiles (3
+groups x 32 tilings) of every book's latest observation; features(vars) returns a fresh tensor for any f32 [n, V] states, and with
+actions=... also the tile indices of that action per row, (sums, idx).  tile_index(sums, actions) is the contract in torch, in int64:
+(sums + .tile_terms[group, action]) mod memory_size -- for all nine actions from the one [n, 96] tensor, 384 bytes per state.
+update(step, actions, vars=None) adds step[s] to each of the 96 weights of (row s, actions[s]): the caller's whole per-tile amount
+(for the learner's own rule pass alpha * delta / 32), on the engine's stream; act(), eval_step and td_step use the new weights in
+the next call.
+
+    sums = env.features()                                                    # [B, 96]
+    q_sa = theta[env.tile_index(sums, a)].sum(-1)                            # Q(s, a) for any theta tensor a learner keeps
+    env.update((alpha / 32) * (target - q_sa), a)                            # semi-gradient step on the engine's own weights
+
+A VecEnv that calls none of the three allocates and launches nothing for them.
+
 step() reads the actions from the tensor's device memory and writes into five persistent tensors (lob_vec_step,
 include/lob_engine.h): no copy to or from the host and no synchronisation.  The engine runs on a stream of its own; it is made
 to wait for torch's current stream before the call (the actions are ready) and torch's current stream for the engine's after it
@@ -83,6 +98,7 @@ class VecEnv:
             self.hist_out = abi.VecHistOut(self.hist_levels.data_ptr(), self.hist_trades.data_ptr(), self.hist_time_ms.data_ptr(),
                                            self.hist_valid.data_ptr(), self.hist_rec.data_ptr())
         self.act_actions = self.act_q = self.act_out = None   # (allocated by the first act())
+        self.feat_sums = self._tile_terms = None   # (allocated by the first features() / tile_index())
         self.stream = torch.cuda.ExternalStream(eng.lob_stream(), device=dev)
         self.bad_actions = 0
         # (the zero fills above ran on torch's stream: the engine's first write must come after them)
@@ -152,6 +168,73 @@ class VecEnv:
         cur.wait_stream(self.stream)
         vars.record_stream(cur)           # (as step() does with the actions)
         return q
+
+    @property
+    def tile_terms(self):
+        """lob_vec_terms: the action terms of the tile hash, int64 [3, 9] (group, action) on the device, reduced mod memory_size;
+        made on first use."""
+        if self._tile_terms is None:
+            self._tile_terms = torch.tensor(self.eng.vec_terms(), dtype=torch.int64, device=self.device)
+        return self._tile_terms
+
+    def _rows(self, vars, who):
+        if (not isinstance(vars, torch.Tensor) or vars.dtype != torch.float32 or not vars.is_cuda or vars.device != self.device
+                or vars.dim() != 2 or vars.shape[1] != self.V or vars.shape[0] < 1 or not vars.is_contiguous()):
+            raise ValueError("VecEnv.%s: vars must be a contiguous float32 CUDA tensor of shape (n, %d) on the engine's device" % (who, self.V))
+        return vars.shape[0]
+
+    def _vec(self, t, dtype, n, who, what):
+        if (not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or t.device != self.device or t.shape != (n,)
+                or not t.is_contiguous()):
+            raise ValueError("VecEnv.%s: %s must be a contiguous %s CUDA tensor of shape (%d,) on the engine's device"
+                             % (who, what, str(dtype).replace("torch.", ""), n))
+
+    def features(self, vars=None, actions=None):
+        """lob_vec_features: the hash sums of the 96 tiles of every state, int32 [n, 96].  vars None: the books' latest observation,
+        into the persistent .feat_sums (overwritten by the next call: clone what must be kept); else f32 [n, V] states and a fresh
+        tensor.  With actions (int32 [n]) it returns (sums, idx): idx int32 [n, 96], fresh, the tile indices of that action per row
+        (-1 throughout a row whose action is out of range) -- tile_index(sums, actions) without the gather."""
+        n = self.B if vars is None else self._rows(vars, "features")
+        if actions is not None:
+            self._vec(actions, torch.int32, n, "features", "actions")
+        if vars is None:
+            if self.feat_sums is None:
+                self.feat_sums = torch.zeros((self.B, abi.N_TILES), dtype=torch.int32, device=self.device)
+            sums = self.feat_sums
+        else:
+            sums = torch.empty((n, abi.N_TILES), dtype=torch.int32, device=self.device)
+        idx = None if actions is None else torch.empty((n, abi.N_TILES), dtype=torch.int32, device=self.device)
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)      # the rows and actions are ready (and whoever still reads .feat_sums is done)
+        self.eng.vec_features(None if vars is None else vars.data_ptr(), n, None if actions is None else actions.data_ptr(),
+                              abi.VecFeatOut(sums.data_ptr(), None if idx is None else idx.data_ptr()))
+        cur.wait_stream(self.stream)
+        for t in (vars, actions):
+            if t is not None:
+                t.record_stream(cur)      # (as step() does with the actions)
+        return sums if actions is None else (sums, idx)
+
+    def tile_index(self, sums, actions):
+        """The contract of lob_vec_features in torch: (sums[s, p] + tile_terms[p // 32, actions[s]]) mod memory_size, int64 [n, 96]
+        -- the weights of (row s, actions[s]); Engine.features' [s, a, :] for a = actions[s].  actions: integers in 0 .. 8, [n]."""
+        terms = self.tile_terms[:, actions.long()].t().repeat_interleave(32, dim=1)   # [n, 96]
+        return (sums.long() + terms) % int(self.eng.M)
+
+    def update(self, step, actions, vars=None, second=False):
+        """lob_vec_update: theta[tile] += step[s] over the 96 tiles of (row s, actions[s]); step f64 [n], actions int32 [n]; vars None:
+        the books' latest observation (n = B; under private theta book s's own vector), else f32 [n, V] states (book 0's vector under
+        private theta).  second: theta_b (double Q only).  A row with step 0.0 writes nothing; a row whose action is out of range is
+        skipped and counted (status())."""
+        n = self.B if vars is None else self._rows(vars, "update")
+        self._vec(step, torch.float64, n, "update", "step")
+        self._vec(actions, torch.int32, n, "update", "actions")
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)      # the steps, actions and rows are ready
+        self.eng.vec_update(None if vars is None else vars.data_ptr(), n, actions.data_ptr(), step.data_ptr(), second)
+        cur.wait_stream(self.stream)
+        for t in (step, actions, vars):
+            if t is not None:
+                t.record_stream(cur)      # (as step() does with the actions)
 
     def _mask_ptr(self, mask, who):
         if mask is None:

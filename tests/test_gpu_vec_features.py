@@ -1,0 +1,478 @@
+"""lob_vec_terms / lob_vec_features / lob_vec_update: the tile features of a state and external weight updates, from device memory to
+device memory.
+
+The yardsticks are the oracle (tests/oracle_lib.py: oracle_tiles, the oracle's weights, its learner steps) and lob_theta_get -- never a
+second engine, never the kernel under test.  Everything is compared for equality unless stated: the updates use dyadic steps
+(k * 2^-20, |k| < 2^20, at most 4 096 rows of 96 tiles: every partial sum is below 2^19 and a multiple of 2^-20, 39 bits, exact in
+f64), so the order of the atomics cannot matter; the learner runs after an update are compared as the rest of the suite compares
+them (tests/parity.py compare_learner_step: exactly under private theta, to 1e-9 under shared theta, where the learner's own atomics
+come in whatever order the hardware makes them).  The device buffers are plain hipMalloc memory (no torch in this process: one HIP
+runtime per process, rl_markets_amd/abi.py); the torch-facing wrapper runs in a process of its own
+(tests/vec_features_torch_child.py).
+
+Q(s, a) is not the plain sum over the 96 tiles: the reference adds 32 x w0 (group 0), 32 x w1 (group 1) and 64 x w2 (groups 1 AND
+2; quirk Q3, tests/test_gpu_vec_act.py cpu_sum), so the values expected of lob_q_values after an update are cpu_sum's over the
+updated weights."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from rl_markets_amd import abi, engine
+from rl_markets_amd.engine import LobError
+from tests import oracle_lib as ol
+from tests.parity import compare_learner_step
+from tests.test_gpu_vec_act import DevArray, DevVec, cpu_sum, make_params, streams
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NA, NT = abi.LOB_N_ACTIONS, 96
+SA, QL, DQ, PRIV, SHARED = abi.ALGO_SARSA, abi.ALGO_QLAMBDA, abi.ALGO_DOUBLE_Q, abi.THETA_PRIVATE, abi.THETA_SHARED
+MS = [1, 65, 1 << 16, (1 << 27) + 1, (1 << 31) - 1]
+BAD_ACTIONS = np.array([-1, NA, 2 ** 31 - 1, -2 ** 31, 64], np.int64)
+
+
+def special_rows(V):
+    """NaN, +-inf, +-1e30, negative values and exact tile boundaries (k / 32 and the floats next to them): in every variable, then
+    in one variable of an ordinary row."""
+    vals = [np.nan, np.inf, -np.inf, 1e30, -1e30, -1.0, -0.03125, 0.03125, np.nextafter(np.float32(0.5), np.float32(1)),
+            np.nextafter(np.float32(0.5), np.float32(0)), -7.96875, 2.0 ** 26]
+    rows = [np.full(V, v, np.float32) for v in vals]
+    for k, v in enumerate(vals):
+        r = np.linspace(-3, 3, V).astype(np.float32)
+        r[k % V] = v
+        rows.append(r)
+    return np.stack(rows)
+
+
+def make_rows(n, V, seed):
+    """n rows: the special ones first (as many as fit), random ones behind them."""
+    rng = np.random.default_rng(seed)
+    rows = rng.uniform(-12, 12, size=(n, V)).astype(np.float32)
+    sp = special_rows(V)[:n]
+    rows[:len(sp)] = sp
+    return rows
+
+
+def tiles(M, rows):
+    rows = np.ascontiguousarray(rows, np.float32)
+    f = np.zeros((rows.shape[0], NA, NT), np.int32)
+    ol.load().oracle_tiles(M, ol.ptr(rows), rows.shape[1], rows.shape[0], ol.ptr(f))
+    return f
+
+
+def terms96(eng):
+    """lob_vec_terms as [9][96]: the term of (group of position p, action a)."""
+    t = np.array(eng.vec_terms(), np.int64)          # [3][9]
+    assert t.shape == (3, NA) and (t >= 0).all() and (t < eng.M).all()
+    return np.repeat(t.T, 32, axis=1)                 # [9][96]
+
+
+def check_contract(eng, sums, F, tag):
+    assert (sums >= 0).all() and (sums < eng.M).all(), tag + ": 0 <= sums < M"
+    got = (sums.astype(np.int64)[:, None, :] + terms96(eng)[None]) % eng.M
+    np.testing.assert_array_equal(got, F, err_msg=tag + ": (sums + terms) mod M against oracle_tiles, all nine actions")
+
+
+def chosen(F, actions):
+    ok = (actions >= 0) & (actions < NA)
+    want = np.full((F.shape[0], NT), -1, np.int32)
+    want[ok] = F[np.nonzero(ok)[0], actions[ok]]
+    return want
+
+
+def dyadic(rng, n):
+    return rng.integers(-(1 << 20) + 1, 1 << 20, size=n).astype(np.float64) * 2.0 ** -20
+
+
+def plain_engine(p, B, n_events=200):
+    eng = engine.Engine(p, B)
+    eng.load_events(streams(p, B, n_events))
+    return eng
+
+
+# ---- 1. free-standing rows ----------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("M", MS)
+def test_free_standing_rows_against_oracle_tiles(M):
+    """n = 1, 5, 67 and 20 000 (more than the grid's waves can take at once at any size of the chip's grid: 2 048 x 4; the waves take a
+    second and a third state), before any lob_reset.  One engine per table size: private theta, one book -- features read no weight."""
+    p = make_params(SA, PRIV, mem=M)
+    V = p.n_vars
+    eng = engine.Engine(p, 1)
+    rng = np.random.default_rng(5)
+    for n in (1, 5, 67, 20000):
+        tag = "M=%d n=%d" % (M, n)
+        rows = make_rows(n, V, 100 + n)
+        actions = rng.integers(0, NA, size=n).astype(np.int64)
+        bad_at = rng.choice(n, size=min(n // 3, 40), replace=False) if n > 1 else np.array([], np.int64)
+        actions[bad_at] = BAD_ACTIONS[np.arange(len(bad_at)) % len(BAD_ACTIONS)]
+        actions = actions.astype(np.int32)
+        F = tiles(M, rows)
+        dv, da = DevArray((n, V), np.float32), DevArray(n, np.int32)
+        dv.upload(rows)
+        da.upload(actions)
+        ds, di = DevArray((n, NT), np.int32), DevArray((n, NT), np.int32)
+        eng.vec_features(dv.ptr, n, da.ptr, abi.VecFeatOut(ds.ptr, di.ptr))
+        eng.sync()
+        sums, idx = ds.download(), di.download()
+        check_contract(eng, sums, F, tag)
+        np.testing.assert_array_equal(idx, chosen(F, actions), err_msg=tag + ": idx is the chosen action's plane, -1 for an invalid action")
+        if n > 1:
+            assert (idx[bad_at] == -1).all() and len(bad_at) > 0
+        # one output wanted: the other buffer keeps its fill pattern
+        s2, i2 = DevArray((n, NT), np.int32), DevArray((n, NT), np.int32)
+        eng.vec_features(dv.ptr, n, None, abi.VecFeatOut(s2.ptr, None))
+        eng.sync()
+        np.testing.assert_array_equal(s2.download(), sums, err_msg=tag + ": sums alone")
+        assert (i2.download().view(np.uint8) == 0xAB).all(), tag + ": idx not wanted: untouched"
+        s3 = DevArray((n, NT), np.int32)
+        eng.vec_features(dv.ptr, n, da.ptr, abi.VecFeatOut(None, i2.ptr))
+        eng.sync()
+        np.testing.assert_array_equal(i2.download(), idx, err_msg=tag + ": idx alone")
+        assert (s3.download().view(np.uint8) == 0xAB).all(), tag + ": sums not wanted: untouched"
+        for d in (dv, da, ds, di, s2, i2, s3):
+            d.free()
+    assert eng.vec_status() == (abi.LOB_OK, 0), "lob_vec_features counts nothing"
+    eng.close()
+
+
+def test_sums_agree_with_lob_features():
+    """The contract as the header words it: against lob_features' own cube."""
+    p = make_params(SA, SHARED)
+    eng = engine.Engine(p, 4)
+    n, V = 67, p.n_vars
+    rows = make_rows(n, V, 3)
+    dv, ds = DevArray((n, V), np.float32), DevArray((n, NT), np.int32)
+    dv.upload(rows)
+    eng.vec_features(dv.ptr, n, None, abi.VecFeatOut(ds.ptr, None))
+    eng.sync()
+    got = (ds.download().astype(np.int64)[:, None, :] + terms96(eng)[None]) % eng.M
+    np.testing.assert_array_equal(got, eng.features(rows))
+    dv.free()
+    ds.free()
+    eng.close()
+
+
+# ---- 2. the books' form -------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("theta_mode", [PRIV, SHARED], ids=["private", "shared"])
+@pytest.mark.parametrize("B", [1, 8, 70])
+def test_books_form_is_oracle_tiles_of_the_observation(B, theta_mode):
+    p = make_params(SA, theta_mode)
+    V, M = p.n_vars, p.memory_size
+    eng = plain_engine(p, B)
+    dev = DevVec(B, V)
+    ds, di, da = DevArray((B, NT), np.int32), DevArray((B, NT), np.int32), DevArray(B, np.int32)
+    rng = np.random.default_rng(B)
+
+    def check(tag):
+        actions = rng.integers(0, NA, size=B).astype(np.int32)
+        if B > 1:
+            actions[B // 2] = NA
+        da.upload(actions)
+        eng.vec_observe(dev.out)
+        eng.vec_features(None, B, da.ptr, abi.VecFeatOut(ds.ptr, di.ptr))
+        obs = dev.read(eng)["obs"]
+        F = tiles(M, obs)
+        check_contract(eng, ds.download(), F, tag)
+        np.testing.assert_array_equal(di.download(), chosen(F, actions), err_msg=tag + ": idx")
+        return obs
+
+    eng.reset()
+    obs0 = check("after reset")
+    for k in range(6):
+        da.upload(rng.integers(0, NA, size=B).astype(np.int32))
+        eng.vec_step(da.ptr, dev.out)
+        if k == 2:
+            eng.snapshot_save(0)
+            obs_saved = check("at the save")
+    obs1 = check("after six steps")
+    assert (obs1 != obs_saved).any() and (obs_saved != obs0).any(), "the observations have moved: a condition on the inputs"
+    eng.snapshot_restore(0)
+    obs2 = check("after lob_snapshot_restore")
+    np.testing.assert_array_equal(obs2, obs_saved)
+    for d in (dev, ds, di, da):
+        d.free()
+    eng.close()
+
+
+# ---- 3. the update, exact -----------------------------------------------------------------------------------------------------------
+
+def update_case(V, seed, n=4096):
+    """n rows with one state repeated 1 000 times, rows with step 0.0 and rows with invalid actions (some of them with step 0.0 as
+    well: the action is looked at first)."""
+    rng = np.random.default_rng(seed)
+    rows = make_rows(n, V, seed)
+    rep = rng.choice(n, size=min(1000, n // 4), replace=False)
+    rows[rep] = rows[rep[0]]
+    actions = rng.integers(0, NA, size=n).astype(np.int64)
+    actions[rep[:len(rep) // 2]] = 4          # (half of the repeats on ONE (state, action): 500 additions to each of its 96 weights)
+    step = dyadic(rng, n)
+    zero = rng.choice(n, size=n // 10, replace=False)
+    step[zero] = 0.0
+    bad = rng.choice(n, size=n // 16, replace=False)
+    actions[bad] = BAD_ACTIONS[np.arange(len(bad)) % len(BAD_ACTIONS)]
+    return rows, actions.astype(np.int32), step
+
+
+def expected_theta(M, F, actions, step, into=None):
+    th = np.zeros(M, np.float64) if into is None else into
+    ok = (actions >= 0) & (actions < NA)
+    idx = F[np.nonzero(ok)[0], actions[ok]]                      # [n_ok][96]
+    np.add.at(th, idx.ravel(), np.repeat(step[ok], NT))
+    return th
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+@pytest.mark.parametrize("algo,theta_mode", [(SA, SHARED), (QL, SHARED), (DQ, SHARED), (SA, PRIV)], ids=["sarsa-shared", "qlambda-shared", "double_q-shared", "sarsa-private"])
+def test_update_of_free_standing_rows_is_exact(algo, theta_mode):
+    B = 8
+    p = make_params(algo, theta_mode)
+    V, M = p.n_vars, p.memory_size
+    eng = engine.Engine(p, B)            # (no events, no reset: the rows' form needs none)
+    rows, actions, step = update_case(V, 17)
+    n = len(rows)
+    n_bad = int(((actions < 0) | (actions >= NA)).sum())
+    assert n_bad > 0 and (step == 0).sum() > 0 and (step[(actions < 0) | (actions >= NA)] == 0).any()
+    F = tiles(M, rows)
+    dv, da, dstep = DevArray((n, V), np.float32), DevArray(n, np.int32), DevArray(n, np.float64)
+    dv.upload(rows)
+    da.upload(actions)
+    dstep.upload(step)
+    eng.vec_update(dv.ptr, n, da.ptr, dstep.ptr)
+    want = expected_theta(M, F, actions, step)
+    got = eng.theta(0)
+    assert (want != 0).sum() > 1000
+    np.testing.assert_array_equal(bits(got), bits(want), err_msg="theta after the update, bit for bit; every untouched weight is +0.0")
+    assert eng.vec_status() == (abi.LOB_EINVAL, n_bad), "the invalid rows, reported once"
+    assert eng.vec_status() == (abi.LOB_OK, 0), "... and cleared"
+    if theta_mode == PRIV:
+        for b in range(1, B):
+            assert (bits(eng.theta(b)) == 0).all(), "free-standing rows under private theta write book 0's vector only"
+    # lob_q_values of the updated rows: the reference's sum over the updated weights
+    sel = np.arange(0, n, 37)
+    np.testing.assert_array_equal(bits(eng.q_values(rows[sel])), bits(cpu_sum(p, rows[sel], want)), err_msg="lob_q_values after the update")
+    lib = abi.load()
+    if algo == DQ:
+        assert (bits(eng.theta(1)) == 0).all(), "second = 0 leaves theta_b alone"
+        eng.vec_update(dv.ptr, n, da.ptr, dstep.ptr, second=True)
+        np.testing.assert_array_equal(bits(eng.theta(1)), bits(want), err_msg="second = 1: theta_b")
+        np.testing.assert_array_equal(bits(eng.theta(0)), bits(want), err_msg="second = 1 leaves theta alone")
+        assert eng.vec_status() == (abi.LOB_EINVAL, n_bad)
+    else:
+        rc = lib.lob_vec_update(eng.h, C.c_void_p(dv.ptr), n, C.c_void_p(da.ptr), C.c_void_p(dstep.ptr), 1)
+        assert rc == abi.LOB_EINVAL and b"lob_vec_update" in lib.lob_last_error(), "second = 1 without a theta_b"
+        np.testing.assert_array_equal(bits(eng.theta(0)), bits(want), err_msg="the refused call wrote nothing")
+    # a second update on top: additions, not stores
+    eng.vec_update(dv.ptr, n, da.ptr, dstep.ptr)
+    np.testing.assert_array_equal(bits(eng.theta(0)), bits(expected_theta(M, F, actions, step, into=want.copy())), err_msg="twice")
+    assert eng.vec_status() == (abi.LOB_EINVAL, n_bad)
+    for d in (dv, da, dstep):
+        d.free()
+    eng.close()
+
+
+@pytest.mark.parametrize("theta_mode", [PRIV, SHARED], ids=["private", "shared"])
+def test_update_in_the_books_form_writes_each_books_own_vector(theta_mode):
+    B = 70
+    p = make_params(SA, theta_mode)
+    V, M = p.n_vars, p.memory_size
+    eng = plain_engine(p, B)
+    dev = DevVec(B, V)
+    da, dstep = DevArray(B, np.int32), DevArray(B, np.float64)
+    rng = np.random.default_rng(23)
+    eng.reset()
+    for k in range(3):
+        da.upload(rng.integers(0, NA, size=B).astype(np.int32))
+        eng.vec_step(da.ptr, dev.out)
+    obs = dev.read(eng)["obs"]
+    actions = rng.integers(0, NA, size=B).astype(np.int32)
+    actions[[3, 40]] = [-1, NA]
+    step = dyadic(rng, B)
+    step[[5, 41]] = 0.0
+    da.upload(actions)
+    dstep.upload(step)
+    eng.vec_update(None, B, da.ptr, dstep.ptr)
+    F = tiles(M, obs)
+    if theta_mode == SHARED:
+        np.testing.assert_array_equal(bits(eng.theta(0)), bits(expected_theta(M, F, actions, step)))
+    else:
+        for b in range(B):
+            want = expected_theta(M, F[b:b + 1], actions[b:b + 1], step[b:b + 1])
+            np.testing.assert_array_equal(bits(eng.theta(b)), bits(want), err_msg="book %d's own vector" % b)
+            assert (want != 0).any() == (b not in (3, 40, 5, 41))
+    assert eng.vec_status() == (abi.LOB_EINVAL, 2) and eng.vec_status() == (abi.LOB_OK, 0)
+    for d in (dev, da, dstep):
+        d.free()
+    eng.close()
+
+
+# ---- 4. the learner after an update -------------------------------------------------------------------------------------------------
+
+def external_update(eng, orc, p, dev, rng, zero=False):
+    """One dyadic update in the books' form on the engine, and the same on the oracle's live weight views with numpy.  The rows are the
+    ones lob_vec_observe returns (the contract of the books' form)."""
+    B, V, M = eng.B, p.n_vars, p.memory_size
+    eng.vec_observe(dev.out)
+    obs = dev.read(eng)["obs"]
+    actions = rng.integers(0, NA, size=B).astype(np.int32)
+    step = np.zeros(B) if zero else rng.integers(-1024, 1025, size=B).astype(np.float64) * 2.0 ** -10
+    if not zero:
+        step[0] = 0.0
+    if B > 2:
+        actions[1] = NA       # skipped on both sides
+    da, dstep = DevArray(B, np.int32), DevArray(B, np.float64)
+    da.upload(actions)
+    dstep.upload(step)
+    F = tiles(M, obs)
+    for second in ((False, True) if p.algo == DQ else (False,)):
+        eng.vec_update(None, B, da.ptr, dstep.ptr, second=second)
+        get = orc.theta_b if second else orc.theta
+        if p.theta_mode == PRIV:
+            for b in range(B):
+                expected_theta(M, F[b:b + 1], actions[b:b + 1], step[b:b + 1], into=get(b))
+        else:
+            expected_theta(M, F, actions, step, into=get(0))
+    eng.sync()
+    da.free()
+    dstep.free()
+    rc, bad = eng.vec_status()
+    assert bad == (1 if B > 2 else 0) * (2 if p.algo == DQ else 1), "the skipped row, once per call"
+
+
+LEARNER = [("private-sarsa", SA, PRIV, 8, False), ("shared-qlambda", QL, SHARED, 64, False), ("shared-double_q", DQ, SHARED, 64, False),
+           ("shared-sarsa", SA, SHARED, 64, False), ("shared-qlambda-no-memo", QL, SHARED, 64, True)]
+
+
+@pytest.mark.parametrize("kind", ["after-five-steps", "right-after-reset", "all-zero"])
+@pytest.mark.parametrize("name,algo,theta_mode,B,no_memo", LEARNER, ids=[c[0] for c in LEARNER])
+def test_learner_steps_after_an_update_follow_the_oracle(name, algo, theta_mode, B, no_memo, kind, monkeypatch):
+    """The consistency rule: after an external update the written-weights maps, the verdicts and the memo records must be what a
+    step expects -- twenty learner steps behind the update agree with the oracle, whose weights received the same increments."""
+    if no_memo:
+        monkeypatch.setenv("LOB_NO_MEMO", "1")
+    p = make_params(algo, theta_mode)
+    V = p.n_vars
+    rec = streams(p, B)
+    eng = engine.Engine(p, B)
+    eng.load_events(rec)
+    orc = ol.Oracle(p, rec)
+    exact = theta_mode == PRIV
+    kw = dict(exact=exact, rtol=0.0 if exact else 1e-9)
+    dev = DevVec(B, V)
+    rng = np.random.default_rng(31)
+    eng.kernel_timing(True)
+    eng.reset()
+    orc.reset()
+    before = 0 if kind == "right-after-reset" else 5
+    for k in range(before):
+        eng.td_step(1)
+        orc.td_step(1)
+        compare_learner_step(eng, orc, "%s: step %d before the update" % (name, k), **kw)
+    external_update(eng, orc, p, dev, rng, zero=kind == "all-zero")
+    for k in range(20):
+        eng.td_step(1)
+        orc.td_step(1)
+        compare_learner_step(eng, orc, "%s %s: step %d after the update" % (name, kind, k), **kw)
+    memo_launches = eng.kernel_time_ms("memo_kernel")[1]
+    if theta_mode == SHARED and algo != DQ:
+        assert (memo_launches == 0) == no_memo, "shared theta: the memo path unless LOB_NO_MEMO=1"
+    if exact:
+        for b in range(B):
+            np.testing.assert_array_equal(bits(eng.theta(b)), bits(orc.theta(b)), err_msg="theta of book %d at the end" % b)
+    else:
+        np.testing.assert_allclose(eng.theta(0), orc.theta(0), rtol=1e-9, atol=1e-12, err_msg="theta at the end")
+        if algo == DQ:
+            np.testing.assert_allclose(eng.theta(1), orc.theta_b(0), rtol=1e-9, atol=1e-12, err_msg="theta_b at the end")
+    assert (orc.theta(0) != 0).any()
+    dev.free()
+    eng.close()
+    orc.close()
+
+
+# ---- 5. refusals --------------------------------------------------------------------------------------------------------------------
+
+def test_refusals():
+    B = 8
+    p = make_params(SA, SHARED)
+    V = p.n_vars
+    eng = plain_engine(p, B)
+    lib = abi.load()
+    vp = C.c_void_p
+    dv, da, dstep = DevArray((B, V), np.float32), DevArray(B, np.int32), DevArray(B, np.float64)
+    ds, di = DevArray((B, NT), np.int32), DevArray((B, NT), np.int32)
+    dv.upload(np.zeros((B, V)))
+    da.upload(np.zeros(B))
+    dstep.upload(np.zeros(B))
+    both, none = abi.VecFeatOut(ds.ptr, di.ptr), abi.VecFeatOut(None, None)
+
+    def refused(rc, want, name):
+        assert rc == want, (name, rc)
+        assert name.encode() in lib.lob_last_error(), lib.lob_last_error()
+
+    feat = lambda *a: lib.lob_vec_features(eng.h, *a)
+    upd = lambda *a: lib.lob_vec_update(eng.h, *a)
+    # the books' form before the first lob_reset
+    refused(feat(None, B, vp(da.ptr), C.byref(both)), abi.LOB_ESTATE, "lob_vec_features")
+    refused(upd(None, B, vp(da.ptr), vp(dstep.ptr), 0), abi.LOB_ESTATE, "lob_vec_update")
+    # ... the rows' form needs none
+    assert feat(vp(dv.ptr), B, vp(da.ptr), C.byref(both)) == abi.LOB_OK
+    assert upd(vp(dv.ptr), B, vp(da.ptr), vp(dstep.ptr), 0) == abi.LOB_OK
+    eng.reset()
+    refused(feat(vp(dv.ptr), B, vp(da.ptr), None), abi.LOB_EINVAL, "lob_vec_features")            # NULL out
+    refused(feat(vp(dv.ptr), 0, vp(da.ptr), C.byref(both)), abi.LOB_EINVAL, "lob_vec_features")   # n < 1
+    refused(feat(vp(dv.ptr), -3, vp(da.ptr), C.byref(both)), abi.LOB_EINVAL, "lob_vec_features")
+    refused(feat(None, B - 1, vp(da.ptr), C.byref(both)), abi.LOB_EINVAL, "lob_vec_features")      # n != n_books in the books' form
+    refused(feat(vp(dv.ptr), B, None, C.byref(both)), abi.LOB_EINVAL, "lob_vec_features")         # idx without actions
+    refused(upd(vp(dv.ptr), B, None, vp(dstep.ptr), 0), abi.LOB_EINVAL, "lob_vec_update")          # NULL actions
+    refused(upd(vp(dv.ptr), B, vp(da.ptr), None, 0), abi.LOB_EINVAL, "lob_vec_update")             # NULL step
+    refused(upd(vp(dv.ptr), 0, vp(da.ptr), vp(dstep.ptr), 0), abi.LOB_EINVAL, "lob_vec_update")
+    refused(upd(None, B + 1, vp(da.ptr), vp(dstep.ptr), 0), abi.LOB_EINVAL, "lob_vec_update")
+    for second in (2, -1):
+        refused(upd(vp(dv.ptr), B, vp(da.ptr), vp(dstep.ptr), second), abi.LOB_EINVAL, "lob_vec_update")
+    refused(upd(vp(dv.ptr), B, vp(da.ptr), vp(dstep.ptr), 1), abi.LOB_EINVAL, "lob_vec_update")    # no theta_b under SARSA
+    assert lib.lob_vec_terms(eng.h, None) == abi.LOB_EINVAL
+    # both outputs NULL: LOB_OK, nothing launched (sums without actions is fine)
+    eng.kernel_timing(True)
+    assert feat(vp(dv.ptr), B, None, C.byref(none)) == abi.LOB_OK
+    assert feat(None, B, None, C.byref(none)) == abi.LOB_OK
+    eng.sync()
+    assert eng.kernel_time_ms("vec_features_kernel")[1] == 0
+    assert feat(None, B, None, C.byref(abi.VecFeatOut(ds.ptr, None))) == abi.LOB_OK
+    eng.sync()
+    assert eng.kernel_time_ms("vec_features_kernel")[1] == 1
+    # between the halves of a learner step
+    eng.td_step_begin()
+    refused(feat(None, B, vp(da.ptr), C.byref(both)), abi.LOB_ESTATE, "lob_vec_features")
+    refused(feat(vp(dv.ptr), B, vp(da.ptr), C.byref(both)), abi.LOB_ESTATE, "lob_vec_features")
+    refused(upd(None, B, vp(da.ptr), vp(dstep.ptr), 0), abi.LOB_ESTATE, "lob_vec_update")
+    refused(upd(vp(dv.ptr), B, vp(da.ptr), vp(dstep.ptr), 0), abi.LOB_ESTATE, "lob_vec_update")
+    eng.td_step_end()
+    # after a restore both are allowed
+    eng.snapshot_save(0)
+    eng.snapshot_restore(0)
+    assert feat(None, B, vp(da.ptr), C.byref(both)) == abi.LOB_OK
+    assert upd(None, B, vp(da.ptr), vp(dstep.ptr), 0) == abi.LOB_OK
+    eng.sync()
+    assert eng.vec_status() == (abi.LOB_OK, 0)
+    for d in (dv, da, dstep, ds, di):
+        d.free()
+    eng.close()
+
+
+# ---- the torch face -----------------------------------------------------------------------------------------------------------------
+
+def test_vec_env_features_and_update_through_torch():
+    """VecEnv.features() / tile_index() / update() at B = 70: tests/vec_features_torch_child.py in a fresh process of its own (torch
+    must be imported before the engine library is loaded: one HIP runtime per process)."""
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "vec_features_torch_child.py")], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    sys.stdout.write(res.stdout[-4000:])
+    assert res.returncode == 0, "vec_features_torch_child.py failed (%d):\n%s\n%s" % (res.returncode, res.stdout[-4000:], res.stderr[-4000:])
+    assert "vec features OK" in res.stdout
