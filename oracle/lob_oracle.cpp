@@ -1499,6 +1499,11 @@ int oracle_get_rho(oracle_learner* o, double* out, int32_t n) {
     for (int i = 0; i < n; i++) out[i] = o->rho[i];
     return 0;
 }
+int oracle_set_rho(oracle_learner* o, const double* in, int32_t n) {
+    if (n < 0 || (size_t)n > o->rho.size()) return -1;
+    for (int i = 0; i < n; i++) o->rho[i] = in[i];
+    return 0;
+}
 void oracle_get_rec(oracle_learner* o, int32_t book, oracle_step_rec* out) { *out = o->recs[book]; }
 double* oracle_theta(oracle_learner* o, int32_t which) { return o->theta[which].data(); }
 double* oracle_theta_b(oracle_learner* o, int32_t which) { return o->theta_b.empty() ? nullptr : o->theta_b[which].data(); }

@@ -70,6 +70,9 @@ void oracle_set_epsilon(oracle_learner* o, double e);
 void oracle_set_tau(oracle_learner* o, double t);
 /* rho of the R-learning agents: out[n], n = 1 (shared theta) or n_books (private) */
 int oracle_get_rho(oracle_learner* o, double* out, int32_t n);
+/* ... and its counterpart: rho[i] = in[i] (a weight exchange between shards writes the exchanged rho back, as it writes theta
+   through the oracle_theta view) */
+int oracle_set_rho(oracle_learner* o, const double* in, int32_t n);
 /* last step's record for `book` */
 void oracle_get_rec(oracle_learner* o, int32_t book, oracle_step_rec* out);
 double* oracle_theta(oracle_learner* o, int32_t which);

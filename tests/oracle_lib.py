@@ -68,6 +68,8 @@ def load():
     lib.oracle_set_epsilon.argtypes = [vp, C.c_double]
     lib.oracle_set_tau.argtypes = [vp, C.c_double]
     lib.oracle_get_rho.argtypes = [vp, vp, C.c_int32]
+    lib.oracle_set_rho.restype = C.c_int
+    lib.oracle_set_rho.argtypes = [vp, vp, C.c_int32]
     lib.oracle_get_rec.argtypes = [vp, C.c_int32, P(StepRec)]
     lib.oracle_theta.restype = P(C.c_double)
     lib.oracle_theta.argtypes = [vp, C.c_int32]
@@ -174,6 +176,15 @@ class Oracle:
         self.lib.oracle_model_log.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         n = self.lib.oracle_model_log(self.h, ptr(rows), cap)
         return rows[:min(n, cap)].copy()
+
+    def rho(self, n=1):
+        out = np.zeros(n, np.float64)
+        assert self.lib.oracle_get_rho(self.h, ptr(out), n) == 0, "oracle_get_rho"
+        return out
+
+    def set_rho(self, values):
+        a = np.ascontiguousarray(values, dtype=np.float64)
+        assert self.lib.oracle_set_rho(self.h, ptr(a), a.size) == 0, "oracle_set_rho"
 
     def theta_b(self, which=0):
         p = self.lib.oracle_theta_b(self.h, which)

@@ -14,6 +14,7 @@ import pytest
 
 from rl_markets_amd import abi, engine
 from tests import edge_cases as ec
+from tests import exchange_cases as xc
 from tests import hard_streams as hs
 from tests import oracle_lib as ol
 
@@ -67,6 +68,22 @@ def test_tables_around_the_pair_kernel_threshold_are_not_chaotic(M, algo):
     vector four of the six did, at steps 7-9, with any stream tried: tests/edge_cases.py big_table_case.)"""
     p, rec = ec.big_table_case(M, algo)
     assert ec.shadow_cut(p, rec, 1, 40) is None
+
+
+@pytest.mark.parametrize("name", sorted(xc.CASES))
+def test_exchange_schedules_are_not_chaotic(name):
+    """The oracle-compared cases of tests/test_gpu_exchange_edges.py (several shards exchanging their weights and rho, external updates,
+    shards that end at different times): the GPU test runs every one of them to its end, so none may leave its shadow."""
+    cut, periods = xc.shadow_cut(xc.CASES[name])
+    assert cut is None, "%s: the shadow shards take another action at step %d" % (name, cut)
+    if name.startswith("unequal-ends"):
+        first_idle = [min(k for k, m in enumerate(periods) if not m[r]) for r in range(3)]
+        assert max(first_idle) - min(first_idle) >= 3 and not any(periods[-1]), first_idle
+
+
+def test_an_exchange_right_after_the_first_reset_is_not_chaotic():
+    cut, _ = xc.shadow_cut(xc.case(abi.ALGO_QLAMBDA, 3, ops=[("x",), ("step", 16), ("x",), ("step", 4)]))
+    assert cut is None
 
 
 def test_policy_sweep_holds_every_algorithm_and_measure():

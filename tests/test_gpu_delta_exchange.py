@@ -16,6 +16,7 @@ import pytest
 from rl_markets_amd import abi, engine
 from rl_markets_amd.parallel import EngineBackend, ShardedLearner, shard_books
 from tests import oracle_lib as ol
+from tests.exchange_ref import rank_sum
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,17 +43,20 @@ def h2d(ptr, arr):
     assert hip().hipMemcpy(C.c_void_p(ptr), a.ctypes.data_as(C.c_void_p), a.size * 8, 1) == 0
 
 
-def make_shards(algo, total=12, world=2, M=1 << 16, n_events=200):
+def make_shards(algo, total=12, world=2, M=1 << 16, n_events=200, tweak=None):
+    """n_events: one stream length for all shards, or one per shard; tweak(p): further parameters of every shard."""
     g = engine.default_gen_params()
-    g.n_events = n_events
     engs, orcs = [], []
     for r in range(world):
+        g.n_events = n_events[r] if isinstance(n_events, (list, tuple)) else n_events
         first, n = shard_books(total, world, r)
         p = engine.default_params()
         p.memory_size = M
         p.algo = algo
         p.book_id_offset = first
-        rec = engine.gen_stream_host(g, p.depth, p.max_trades, first, n)
+        if tweak:
+            tweak(p)
+        rec = engine.gen_stream_host(g, p.depth, p.max_trades, p.book_id_offset, n)
         e = engine.Engine(p, n)
         e.load_events(rec)
         e.reset()
@@ -64,10 +68,15 @@ def make_shards(algo, total=12, world=2, M=1 << 16, n_events=200):
     return engs, orcs
 
 
-def host_allreduce(engs):
-    """What lob_theta_allreduce does on every rank, the sum over ranks formed on the host."""
+def host_allreduce(engs, seen=None):
+    """What lob_theta_allreduce does on every rank, the sum over ranks formed on the host (in rank order).  seen: a dict that takes
+    what was read -- the ranks' delta buffers before they are summed, their common length, the sum."""
     bufs = [e.delta_begin() for e in engs]
-    tot = sum(d2h(ptr, n) for ptr, n in bufs)
+    assert len({n for _, n in bufs}) == 1, "every rank must offer the same number of doubles"
+    parts = [d2h(ptr, n) for ptr, n in bufs]
+    tot = rank_sum(parts)
+    if seen is not None:
+        seen.update(deltas=parts, count=bufs[0][1], total=tot)
     for (ptr, n), e in zip(bufs, engs):
         h2d(ptr, tot)
         e.delta_apply()
@@ -106,9 +115,10 @@ def d2h_u32(ptr, n):
     return out
 
 
-def host_sparse_allreduce(engs):
+def host_sparse_allreduce(engs, seen=None):
     """What lob_theta_allreduce does on the sparse path, the two collectives formed on the host: all-gather of the ranks'
-    written-weights maps, union + pack on every rank, all-reduce (SUM) of the packed deltas, scatter."""
+    written-weights maps, union + pack on every rank, all-reduce (SUM, in rank order) of the packed deltas, scatter.  seen: a dict
+    that takes what was read -- the ranks' maps, their packed buffers before they are summed, the count, the sum."""
     world = len(engs)
     maps = [e.delta_sparse_maps(world) for e in engs]
     own = [d2h_u32(o, w) for o, _, w in maps]
@@ -120,9 +130,13 @@ def host_sparse_allreduce(engs):
     counts = {n for _, n in packed}
     assert len(counts) == 1, "every rank must arrive at the same compact layout"
     n = counts.pop()
-    tot = sum(d2h(ptr, n) for ptr, _ in packed)
+    parts = [d2h(ptr, n) for ptr, _ in packed]
+    tot = rank_sum(parts) if n else np.zeros(0)
+    if seen is not None:
+        seen.update(maps=own, packed=parts, count=n, total=tot)
     for (ptr, _), e in zip(packed, engs):
-        h2d(ptr, tot)
+        if n:
+            h2d(ptr, tot)
         e.delta_sparse_apply()
     return n
 

@@ -26,6 +26,7 @@ from rl_markets_amd.engine import LobError
 from tests import oracle_lib as ol
 from tests.parity import compare_learner_step
 from tests.test_gpu_vec_act import DevArray, DevVec, cpu_sum, make_params, streams
+from tests.tile_ref import expected_theta, tiles
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -55,13 +56,6 @@ def make_rows(n, V, seed):
     sp = special_rows(V)[:n]
     rows[:len(sp)] = sp
     return rows
-
-
-def tiles(M, rows):
-    rows = np.ascontiguousarray(rows, np.float32)
-    f = np.zeros((rows.shape[0], NA, NT), np.int32)
-    ol.load().oracle_tiles(M, ol.ptr(rows), rows.shape[1], rows.shape[0], ol.ptr(f))
-    return f
 
 
 def terms96(eng):
@@ -217,14 +211,6 @@ def update_case(V, seed, n=4096):
     bad = rng.choice(n, size=n // 16, replace=False)
     actions[bad] = BAD_ACTIONS[np.arange(len(bad)) % len(BAD_ACTIONS)]
     return rows, actions.astype(np.int32), step
-
-
-def expected_theta(M, F, actions, step, into=None):
-    th = np.zeros(M, np.float64) if into is None else into
-    ok = (actions >= 0) & (actions < NA)
-    idx = F[np.nonzero(ok)[0], actions[ok]]                      # [n_ok][96]
-    np.add.at(th, idx.ravel(), np.repeat(step[ok], NT))
-    return th
 
 
 def bits(a):
