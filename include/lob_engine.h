@@ -603,6 +603,36 @@ int lob_vec_terms(lob_engine* e, int32_t host_out[27]);   /* [group][action], re
 int lob_vec_features(lob_engine* e, const float* dev_vars, int32_t n, const int32_t* dev_actions, const lob_vec_feat_out* out);
 int lob_vec_update(lob_engine* e, const float* dev_vars, int32_t n, const int32_t* dev_actions, const double* dev_step, int32_t second);
 
+/* ---- vector-env interface: one-step look-ahead over the nine actions, on the device ---
+ * The environment as a model: "what would each action give me from here?" -- for one-step expectimax targets
+ * r(s, a) + gamma * max Q(s'_a, .) (lob_vec_q on the result), exact advantage baselines, hindsight labels, a teacher that looks one
+ * step ahead.  One launch instead of lob_snapshot_save + nine times (lob_vec_step, a copy, lob_snapshot_restore), and no snapshot
+ * slot is taken.
+ *   lob_vec_peek_out: where the results go, DEVICE pointers on the engine's GPU, written in stream order; a NULL member is skipped.
+ * Every tensor is action-major: plane a = elements [a * n_books, (a + 1) * n_books).
+ *   lob_vec_peek: for every action a whose bit is set in action_mask (LOB_PEEK_ALL: all nine), plane a holds bit for bit what
+ * lob_vec_step would have written to obs / reward / terminal / stepped had every book been given action a at this point -- a book
+ * that is over: stepped 0, reward +0.0, obs = the state of its last completed step, terminal as it stands; a step that runs out of
+ * data (necessarily under all nine actions alike): stepped 0, reward +0.0, terminal 2, obs kept.  The planes of actions that are not
+ * in the mask are not written.
+ *   Nothing of the engine changes: no book, no PnL window, no state vector, no step header, no memo / verdict / hit-list word, no
+ * counter of lob_get_counters, no step number, no step-log row and no random stream; the next lob_vec_step, lob_step or learner call
+ * gives what it would have given without the call.  (The one exception is the engine's sticky error word: a condition on the event
+ * data that the step with action a would have reported -- LOB_EDATA from lob_vec_status -- is reported by the look-ahead as well.)
+ *   Enqueued on the engine's stream (lob_stream) as one launch, returns at once: no host read, no allocation, no copy and no
+ * synchronisation.  Allowed after lob_snapshot_restore (it reads the environment only).  LOB_EINVAL, with a message naming the call:
+ * a NULL engine or out, action_mask 0 or with a bit at or above LOB_N_ACTIONS.  LOB_ESTATE: before the first lob_reset, between
+ * lob_td_step_begin and lob_td_step_end, and on a stream whose market track is a ring (longer than LOB_TRACK_RING events: the
+ * snapshot calls are refused there too).  All four members NULL: LOB_OK, nothing is launched. */
+#define LOB_PEEK_ALL 0x1FFu
+typedef struct lob_vec_peek_out {   /* DEVICE pointers on the engine's GPU; any may be NULL = not wanted; action-major planes */
+    float*   obs;                   /* [9][n_books][n_vars] */
+    double*  reward;                /* [9][n_books] */
+    uint8_t* terminal;              /* [9][n_books] */
+    int32_t* stepped;               /* [9][n_books] */
+} lob_vec_peek_out;
+int lob_vec_peek(lob_engine* e, uint32_t action_mask, const lob_vec_peek_out* out);
+
 /* ---- episode statistics of the whole batch ---------------------------------
  * What the reference logs about ONE environment after an episode -- the `training_log` row of Runner::RunEpisode
  * (src/experiment/serial.cpp:81-88: getEpisodeReward, getEpisodePnL, total_ticks), Base::writeStats and getTotalTransactions

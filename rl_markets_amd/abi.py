@@ -185,6 +185,15 @@ class VecFeatOut(C.Structure):
     _fields_ = [("sums", C.c_void_p), ("idx", C.c_void_p)]
 
 
+# lob_vec_peek: the mask of all nine actions (LOB_PEEK_ALL)
+PEEK_ALL = 0x1FF
+
+
+class VecPeekOut(C.Structure):
+    """lob_vec_peek_out: where lob_vec_peek writes, four DEVICE addresses (0 = not wanted) of action-major tensors: plane a = action a."""
+    _fields_ = [("obs", C.c_void_p), ("reward", C.c_void_p), ("terminal", C.c_void_p), ("stepped", C.c_void_p)]
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LOB_ENGINE_LIB: an experiment build of the same library (tools/exp_prof.py, tools/exp_variants.sh)
 LIB_PATH = os.environ.get("LOB_ENGINE_LIB") or os.path.join(_HERE, "csrc", "liblob_engine.so")
@@ -260,6 +269,7 @@ def load():
         "lob_vec_terms": (C.c_int, [vp, P(C.c_int32)]),
         "lob_vec_features": (C.c_int, [vp, vp, C.c_int32, vp, P(VecFeatOut)]),
         "lob_vec_update": (C.c_int, [vp, vp, C.c_int32, vp, vp, C.c_int32]),
+        "lob_vec_peek": (C.c_int, [vp, C.c_uint32, P(VecPeekOut)]),
         "lob_snapshot_save": (C.c_int, [vp, C.c_int32, C.c_void_p]),
         "lob_snapshot_restore": (C.c_int, [vp, C.c_int32, C.c_void_p]),
         "lob_snapshot_free": (C.c_int, [vp, C.c_int32]),

@@ -1568,6 +1568,37 @@ int lob_vec_act(lob_engine* e, int32_t mode, const lob_vec_act_out* out) {
     return LOB_OK;
 }
 
+// What lob_vec_step would write under each action of the mask, into the caller's device buffers (lob_tu_vecpeek.hip vec_peek_kernel;
+// DESIGN.md 7j): one launch on the engine's stream, nothing read back, nothing of the engine's state changed -- no step number, no
+// memo list, no step-log row, no refill of the track.  Not refused after lob_snapshot_restore: it reads the environment only.
+// Refused on a ring track, like the snapshots: the look-ahead reads the entries ahead of the cursor exactly as the step does, but
+// that they are all there between two refills whenever it is called has not been shown.
+int lob_vec_peek(lob_engine* e, uint32_t action_mask, const lob_vec_peek_out* out) {
+    if (!e || !out) { lob_set_error("lob_vec_peek: NULL argument"); return LOB_EINVAL; }
+    if (action_mask == 0 || (action_mask & ~(uint32_t)LOB_PEEK_ALL)) {
+        lob_set_error("lob_vec_peek: action_mask " + std::to_string(action_mask) + " is empty or has a bit at or above LOB_N_ACTIONS"); return LOB_EINVAL;
+    }
+    int rc = need_reset(e, "lob_vec_peek");
+    if (rc) return rc;
+    if ((rc = not_mid_step(e, "lob_vec_peek"))) return rc;
+    if (e->chunked) { lob_set_error("lob_vec_peek: the market track of this stream is a ring (longer than LOB_TRACK_RING events)"); return LOB_ESTATE; }
+    if (!out->obs && !out->reward && !out->terminal && !out->stepped) return LOB_OK;
+    HIPCHK(hipSetDevice(e->device));
+    PeekSrc a;
+    a.B = e->B; a.Bpad = (e->B + 63) / 64 * 64;
+    a.n_act = 0;
+    for (int k = 0; k < 12; k++) a.act[k] = 0;
+    for (int k = 0; k < LOB_N_ACTIONS; k++)
+        if (action_mask >> k & 1u) a.act[a.n_act++] = (uint8_t)k;
+    a.out = *out;
+    {
+        TimedLaunch t(e, "vec_peek_kernel", nullptr, true);
+        lobk_vec_peek(e->stream, e->P.T <= 2, (const DevParams*)e->P_dev, e->S, a);
+    }
+    HIPCHK(hipGetLastError());
+    return LOB_OK;
+}
+
 // lob_q_values with both ends in device memory: the same kernel over the caller's rows, under theta (book 0's under private theta).
 int lob_vec_q(lob_engine* e, const float* dev_vars, int32_t n, double* dev_q) {
     if (!e || !dev_vars || !dev_q || n < 1) { lob_set_error("lob_vec_q: bad argument"); return LOB_EINVAL; }

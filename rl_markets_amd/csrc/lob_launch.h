@@ -1,7 +1,7 @@
-// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is twelve
+// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is thirteen
 // .hip files built in parallel: lob_engine.hip -- the C ABI's host side and the update / memo / trace kernels --, lob_tu_env.hip,
 // lob_tu_prepass.hip, lob_tu_learn.hip, lob_tu_stats.hip, lob_tu_steplog.hip, lob_tu_vec.hip, lob_tu_vecbook.hip, lob_tu_vechist.hip, lob_tu_snapshot.hip,
-// lob_tu_vecact.hip, lob_tu_vecfeat.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
+// lob_tu_vecact.hip, lob_tu_vecfeat.hip, lob_tu_vecpeek.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
 // lob_engine.hip used when it held the launches itself.  Kernels measured and lost (NOTES.md "Round 4") are only compiled with
 // -DLOB_EXPERIMENTS (tools/exp_variants.sh); a product build answers LOB_EXPERIMENTS-only requests with the product kernel.
 #ifndef LOB_LAUNCH_H
@@ -218,6 +218,19 @@ struct VecFeatSrc {
 };
 // vec_feat_kernel<books, update>: a persistent grid of at most LOB_VECFEAT_MAX_BLOCKS blocks, sized from the compute units (`n_cus`)
 void lobk_vec_feat(hipStream_t st, int n_cus, const DevParams* Pd, const DevState* Sd, const uint32_t* rnd, const VecFeatSrc& a);
+
+// ---- lob_tu_vecpeek.hip ----
+// What lob_vec_peek (include/lob_engine.h) takes beyond the parameters and the state, which vec_peek_kernel receives as env_kernel
+// does: the actions of the mask in ascending order, the batch and its size rounded up to whole waves -- block i of the grid is action
+// act[i / (Bpad / 64)] over the books 64 * (i % (Bpad / 64)) ... -- and the caller's device buffers, action-major planes.
+struct PeekSrc {
+    i32 B, Bpad;           // books; B rounded up to a multiple of 64
+    i32 n_act;             // actions in the mask
+    uint8_t act[12];       // [n_act] the set bits of the mask, ascending
+    lob_vec_peek_out out;  // obs [9][B][V], reward [9][B], terminal [9][B], stepped [9][B]; NULL: not wanted
+};
+// vec_peek_kernel<t2>: n_act * Bpad / 64 one-wave blocks; `t2` as lobk_env's
+void lobk_vec_peek(hipStream_t st, bool t2, const DevParams* Pd, const DevState& S, const PeekSrc& a);
 
 // ---- lob_tu_learn.hip ----
 // learn_q_pair_kernel / learn_q_lane_kernel<algo, vt, tr>: vt = 8 when the state has eight variables (else 0)

@@ -335,6 +335,14 @@ class Engine:
         (vec_status).  Enqueued on the engine's stream."""
         self._check(self.lib.lob_vec_update(self.h, C.c_void_p(vars_ptr), int(n), C.c_void_p(actions_ptr), C.c_void_p(step_ptr), 1 if second else 0))
 
+    def vec_peek(self, mask, out):
+        """lob_vec_peek: for every action whose bit is set in `mask` (abi.PEEK_ALL: all nine), what vec_step would write had every
+        book been given that action now, into plane `action` of the device buffers of `out` (abi.VecPeekOut: obs f32 [9, B, V],
+        reward f64 [9, B], terminal uint8 [9, B], stepped int32 [9, B]; 0 = not wanted) -- and nothing of the engine changes.  The
+        planes of the other actions are not written.  One launch, enqueued on the engine's stream; works after snapshot_restore();
+        refused on a ring-mode stream."""
+        self._check(self.lib.lob_vec_peek(self.h, int(mask), C.byref(out)))
+
     def snapshot_save(self, slot, mask_ptr=None):
         """lob_snapshot_save: the environment state of the books selected by the DEVICE mask at address `mask_ptr` (uint8 [B],
         nonzero selects; None: every book, which (re)starts the slot) into snapshot slot `slot` (0 .. abi.MAX_SNAPSHOTS - 1);

@@ -55,6 +55,17 @@ the next call.
 
 A VecEnv that calls none of the three allocates and launches nothing for them.
 
+peek(actions=None) is the environment as a model (lob_vec_peek): for each of the nine actions -- or those listed -- what step() would
+return had every book been given that action now, in .peek_obs f32 [9, B, V], .peek_reward f64 [9, B], .peek_terminal uint8 [9, B]
+and .peek_stepped int32 [9, B] (plane a = action a; planes not asked for keep their last contents), in one launch, and the books
+stay exactly where they are.  One-step expectimax targets under the engine's own weights:
+
+    o, r, t, s = env.peek()
+    q = env.q_values(o.view(9 * B, V)).view(9, B, 9).max(-1).values
+    target = r + gamma * q * (t == 0)
+
+Not available on a ring-mode stream.  A VecEnv that never calls peek() allocates and launches nothing for it.
+
 step() reads the actions from the tensor's device memory and writes into five persistent tensors (lob_vec_step,
 include/lob_engine.h): no copy to or from the host and no synchronisation.  The engine runs on a stream of its own; it is made
 to wait for torch's current stream before the call (the actions are ready) and torch's current stream for the engine's after it
@@ -99,6 +110,7 @@ class VecEnv:
                                            self.hist_valid.data_ptr(), self.hist_rec.data_ptr())
         self.act_actions = self.act_q = self.act_out = None   # (allocated by the first act())
         self.feat_sums = self._tile_terms = None   # (allocated by the first features() / tile_index())
+        self.peek_obs = self.peek_reward = self.peek_terminal = self.peek_stepped = self.peek_out = None   # (allocated by the first peek())
         self.stream = torch.cuda.ExternalStream(eng.lob_stream(), device=dev)
         self.bad_actions = 0
         # (the zero fills above ran on torch's stream: the engine's first write must come after them)
@@ -154,6 +166,39 @@ class VecEnv:
         self.eng.vec_act(self._ACT_MODES[mode], self.act_out)
         cur.wait_stream(self.stream)
         return self.act_actions
+
+    def peek(self, actions=None):
+        """lob_vec_peek: one-step look-ahead.  actions: an iterable of ints in 0 .. 8, None: all nine.  Returns (.peek_obs,
+        .peek_reward, .peek_terminal, .peek_stepped), persistent tensors [9, B, V] / [9, B]: plane a holds what step() would return
+        had every book been given action a now -- a book that is over: stepped 0, reward 0, its last observation; planes not asked
+        for keep their last contents.  Nothing of the environment changes.  The expectimax recipe:
+
+            o, r, t, s = env.peek()
+            q = env.q_values(o.view(9 * B, V)).view(9, B, 9).max(-1).values
+            target = r + gamma * q * (t == 0)
+        """
+        mask = abi.PEEK_ALL
+        if actions is not None:
+            mask = 0
+            for a in actions:
+                if int(a) != a or not 0 <= int(a) < abi.LOB_N_ACTIONS:
+                    raise ValueError("VecEnv.peek: actions must be integers in 0 .. %d" % (abi.LOB_N_ACTIONS - 1))
+                mask |= 1 << int(a)
+            if mask == 0:
+                raise ValueError("VecEnv.peek: no action given")
+        cur = torch.cuda.current_stream(self.device)
+        if self.peek_out is None:
+            n = abi.LOB_N_ACTIONS
+            self.peek_obs = torch.zeros((n, self.B, self.V), dtype=torch.float32, device=self.device)
+            self.peek_reward = torch.zeros((n, self.B), dtype=torch.float64, device=self.device)
+            self.peek_terminal = torch.zeros((n, self.B), dtype=torch.uint8, device=self.device)
+            self.peek_stepped = torch.zeros((n, self.B), dtype=torch.int32, device=self.device)
+            self.peek_out = abi.VecPeekOut(self.peek_obs.data_ptr(), self.peek_reward.data_ptr(), self.peek_terminal.data_ptr(),
+                                           self.peek_stepped.data_ptr())
+        self.stream.wait_stream(cur)      # (the zero fills, and whoever still reads the tensors of the last peek())
+        self.eng.vec_peek(mask, self.peek_out)
+        cur.wait_stream(self.stream)
+        return self.peek_obs, self.peek_reward, self.peek_terminal, self.peek_stepped
 
     def q_values(self, vars):
         """lob_vec_q: Q(s, .) under the engine's weights (theta; book 0's under private theta) for n free-standing states, f32 [n, V]
