@@ -633,6 +633,49 @@ typedef struct lob_vec_peek_out {   /* DEVICE pointers on the engine's GPU; any 
 } lob_vec_peek_out;
 int lob_vec_peek(lob_engine* e, uint32_t action_mask, const lob_vec_peek_out* out);
 
+/* ---- vector-env interface: multi-step look-ahead under action plans, on the device ---
+ * The environment as a model several steps deep: the books rolled forward `horizon` steps under each of `n_plans` candidate plans PER
+ * BOOK -- n-step targets, random-shooting or CEM model-predictive control, "which of these K quote schedules is best from here" -- in
+ * one launch instead of lob_snapshot_save + n_plans times (horizon lob_vec_step, copies, lob_snapshot_restore), and no snapshot slot
+ * is taken.
+ *   dev_actions: DEVICE memory on the engine's GPU, int32 [n_plans][horizon][n_books]: the action of plan p at step h for book b.
+ *   lob_vec_rollout_out: where the results go, DEVICE pointers on the engine's GPU, written in stream order; a NULL member is skipped.
+ * Every tensor is plan-major.
+ *   lob_vec_rollout: take plan p and imagine `horizon` consecutive lob_vec_step calls from the engine's present state, the h-th with
+ * dev_actions[p][h][:].  Bit for bit, reward[p][h][b] is what the h-th call would write to reward[b]; obs[p][b] and terminal[p][b]
+ * are what the last call would write; stepped[p][b] is the sum of the calls' stepped[b].  The rules of every step are
+ * lob_vec_step's: a book steps only if its terminal is 0 at the entry of that step; a book that is over, or a step that runs out of
+ * data, gives reward +0.0 and keeps the obs of the last completed step (if no step of the plan completed: the state the engine holds
+ * now); an action outside [0, LOB_N_ACTIONS) means the book is not stepped at that step and the plan goes on with the next.  Such an
+ * action is NOT counted in the word lob_vec_status reports: padding a plan with -1 is the way to make plans of unequal length.
+ *   ret[p][b] is the discounted sum of the plan's rewards in exactly this order, every operation rounded on its own (no fused
+ * multiply-add): acc = +0.0, d = 1.0; for h = 0 .. horizon - 1: acc = acc + d * r_h, d = d * gamma -- the discount follows h whether
+ * or not the step completed.
+ *   Nothing of the engine changes, as under lob_vec_peek: no book, no PnL window, no state vector, no step header, no memo / verdict /
+ * hit-list word, no counter of lob_get_counters, no step number, no step-log row, no random stream, no snapshot slot; with the same
+ * exception, the engine's sticky error word.
+ *   Enqueued on the engine's stream (lob_stream) as one launch, returns at once: no host read, no copy and no synchronisation -- with
+ * one exception, as for lob_snapshot_save's slot buffers: when the reward is LOB_REWARD_NORMED and 1 < lb_pnl < horizon, the engine
+ * keeps the PnL windows' entries the plans themselves push in a workspace of 2 * lb_pnl * n_plans * (n_books rounded up to 64)
+ * doubles.  The first call that needs it allocates it, a later call that needs a larger one replaces it (allocation and release
+ * synchronise the device); every other call allocates nothing.  lob_destroy releases it.
+ *   Allowed after lob_snapshot_restore and while the step log records.  Refusals carry a message naming the call, and a refused call
+ * writes nothing.  LOB_EINVAL: a NULL engine, out or dev_actions; n_plans outside 1 .. LOB_MAX_ROLLOUT_PLANS; horizon outside
+ * 1 .. LOB_MAX_ROLLOUT_STEPS; gamma NaN or outside [0, 1].  LOB_ESTATE: before the first lob_reset, between lob_td_step_begin and
+ * lob_td_step_end, and on a stream whose market track is a ring (longer than LOB_TRACK_RING events).  LOB_ENOMEM: the workspace does
+ * not fit.  All five members NULL: LOB_OK, nothing is launched. */
+#define LOB_MAX_ROLLOUT_PLANS 64
+#define LOB_MAX_ROLLOUT_STEPS 64
+typedef struct lob_vec_rollout_out {   /* device pointers; NULL = not wanted, not written */
+    float*   obs;       /* [P][B][V]  the observation behind the plan's last step             */
+    double*  reward;    /* [P][H][B]  the reward of every step of the plan                    */
+    uint8_t* terminal;  /* [P][B]     lob_get_terminal's value behind the last step           */
+    int32_t* stepped;   /* [P][B]     how many of the H steps completed, 0 .. H               */
+    double*  ret;       /* [P][B]     the discounted sum of the plan's rewards                */
+} lob_vec_rollout_out;
+int lob_vec_rollout(lob_engine* e, const int32_t* dev_actions /* [P][H][B] */, int n_plans, int horizon,
+                    double gamma, const lob_vec_rollout_out* out);
+
 /* ---- episode statistics of the whole batch ---------------------------------
  * What the reference logs about ONE environment after an episode -- the `training_log` row of Runner::RunEpisode
  * (src/experiment/serial.cpp:81-88: getEpisodeReward, getEpisodePnL, total_ticks), Base::writeStats and getTotalTransactions

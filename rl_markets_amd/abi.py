@@ -194,6 +194,17 @@ class VecPeekOut(C.Structure):
     _fields_ = [("obs", C.c_void_p), ("reward", C.c_void_p), ("terminal", C.c_void_p), ("stepped", C.c_void_p)]
 
 
+# lob_vec_rollout: the most plans and the most steps per plan of one call (LOB_MAX_ROLLOUT_PLANS, LOB_MAX_ROLLOUT_STEPS)
+MAX_ROLLOUT_PLANS = 64
+MAX_ROLLOUT_STEPS = 64
+
+
+class VecRolloutOut(C.Structure):
+    """lob_vec_rollout_out: where lob_vec_rollout writes, five DEVICE addresses (0 = not wanted) of plan-major tensors: obs f32 [P, B, V],
+    reward f64 [P, H, B], terminal uint8 [P, B], stepped int32 [P, B], ret f64 [P, B]."""
+    _fields_ = [("obs", C.c_void_p), ("reward", C.c_void_p), ("terminal", C.c_void_p), ("stepped", C.c_void_p), ("ret", C.c_void_p)]
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LOB_ENGINE_LIB: an experiment build of the same library (tools/exp_prof.py, tools/exp_variants.sh)
 LIB_PATH = os.environ.get("LOB_ENGINE_LIB") or os.path.join(_HERE, "csrc", "liblob_engine.so")
@@ -270,6 +281,7 @@ def load():
         "lob_vec_features": (C.c_int, [vp, vp, C.c_int32, vp, P(VecFeatOut)]),
         "lob_vec_update": (C.c_int, [vp, vp, C.c_int32, vp, vp, C.c_int32]),
         "lob_vec_peek": (C.c_int, [vp, C.c_uint32, P(VecPeekOut)]),
+        "lob_vec_rollout": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_double, P(VecRolloutOut)]),
         "lob_snapshot_save": (C.c_int, [vp, C.c_int32, C.c_void_p]),
         "lob_snapshot_restore": (C.c_int, [vp, C.c_int32, C.c_void_p]),
         "lob_snapshot_free": (C.c_int, [vp, C.c_int32]),

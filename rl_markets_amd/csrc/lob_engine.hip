@@ -198,6 +198,8 @@ struct lob_engine {
     bool lib_pending = false;   // a selection waits for the next lob_reset (in set lib_cur ^ 1, or 0)
     Track* track_dev = nullptr;
     i32* actions_dev = nullptr;
+    f64* roll_ws = nullptr;     // lob_vec_rollout: the PnL windows' entries the plans push (lob_launch.h RolloutSrc::shadow), made by the first
+    size_t roll_ws_elems = 0;   // call that needs it, grown when a later call needs more, never per call
     u64* vec_bad = nullptr;     // lob_vec_step: actions out of range since the last lob_vec_status / lob_reset (one device word)
     i32* vec_upd_tag = nullptr; // lob_vec_update: the number of the last launch that wrote a weight (one device word; lob_launch.h VecFeatSrc)
     i32 vec_upd_launch = 0;     // ... and the number of the last launch (never 0 once used)
@@ -818,6 +820,7 @@ void lob_destroy(lob_engine* e) {
     if (e->slog_stage) hipFree(e->slog_stage);
     for (void* p : e->snap_buf) if (p) hipFree(p);
     if (e->snap_tab) hipFree(e->snap_tab);
+    if (e->roll_ws) hipFree(e->roll_ws);
     if (e->spx_gather) hipFree(e->spx_gather);
     if (e->spx_ev) hipEventDestroy(e->spx_ev);
     if (e->spx_total_host) hipHostFree(e->spx_total_host);
@@ -1594,6 +1597,57 @@ int lob_vec_peek(lob_engine* e, uint32_t action_mask, const lob_vec_peek_out* ou
     {
         TimedLaunch t(e, "vec_peek_kernel", nullptr, true);
         lobk_vec_peek(e->stream, e->P.T <= 2, (const DevParams*)e->P_dev, e->S, a);
+    }
+    HIPCHK(hipGetLastError());
+    return LOB_OK;
+}
+
+// What `horizon` consecutive lob_vec_step calls would write under each of `n_plans` plans, into the caller's device buffers
+// (lob_tu_vecroll.hip vec_rollout_kernel): one launch on the engine's stream, nothing read back, nothing of the engine's
+// state changed.  Allowed and refused where lob_vec_peek is.  The one allocation: the workspace of the PnL windows' entries the plans
+// themselves push, needed when the reward reads the windows (LOB_REWARD_NORMED) and 1 < lb_pnl < horizon -- 2 * lb_pnl * n_plans *
+// Bpad doubles, made by the first call that needs it and grown (hipFree + hipMalloc: both synchronise the device) only by a call
+// that needs more than any before it.
+int lob_vec_rollout(lob_engine* e, const int32_t* dev_actions, int n_plans, int horizon, double gamma, const lob_vec_rollout_out* out) {
+    if (!e || !out || !dev_actions) { lob_set_error("lob_vec_rollout: NULL argument"); return LOB_EINVAL; }
+    if (n_plans < 1 || n_plans > LOB_MAX_ROLLOUT_PLANS) {
+        lob_set_error("lob_vec_rollout: n_plans = " + std::to_string(n_plans) + " is outside [1, " + std::to_string(LOB_MAX_ROLLOUT_PLANS) + "]"); return LOB_EINVAL;
+    }
+    if (horizon < 1 || horizon > LOB_MAX_ROLLOUT_STEPS) {
+        lob_set_error("lob_vec_rollout: horizon = " + std::to_string(horizon) + " is outside [1, " + std::to_string(LOB_MAX_ROLLOUT_STEPS) + "]"); return LOB_EINVAL;
+    }
+    if (!(gamma >= 0.0 && gamma <= 1.0)) { lob_set_error("lob_vec_rollout: gamma = " + std::to_string(gamma) + " is outside [0, 1]"); return LOB_EINVAL; }
+    int rc = need_reset(e, "lob_vec_rollout");
+    if (rc) return rc;
+    if ((rc = not_mid_step(e, "lob_vec_rollout"))) return rc;
+    if (e->chunked) { lob_set_error("lob_vec_rollout: the market track of this stream is a ring (longer than LOB_TRACK_RING events)"); return LOB_ESTATE; }
+    if (!out->obs && !out->reward && !out->terminal && !out->stepped && !out->ret) return LOB_OK;
+    HIPCHK(hipSetDevice(e->device));
+    RolloutSrc a;
+    a.actions = dev_actions;
+    a.B = e->B; a.Bpad = (e->B + 63) / 64 * 64;
+    a.n_plans = n_plans; a.horizon = horizon;
+    a.gamma = gamma;
+    a.shadow = nullptr;
+    a.out = *out;
+    const int w = e->S.pnl_ups.w;
+    if (e->P.reward_measure == LOB_REWARD_NORMED && w > 1 && w < horizon) {
+        const size_t need = 2 * (size_t)w * (size_t)n_plans * (size_t)a.Bpad;
+        if (need > e->roll_ws_elems) {
+            f64* ws = nullptr;
+            if (e->roll_ws) { hipFree(e->roll_ws); e->roll_ws = nullptr; e->roll_ws_elems = 0; }
+            if (hipMalloc((void**)&ws, need * sizeof(f64)) != hipSuccess) {
+                (void)hipGetLastError();
+                lob_set_error("lob_vec_rollout: no room for the PnL windows' workspace (" + std::to_string(need * sizeof(f64)) + " bytes; fewer plans or a shorter horizon per call)");
+                return LOB_ENOMEM;
+            }
+            e->roll_ws = ws; e->roll_ws_elems = need;
+        }
+        a.shadow = e->roll_ws;
+    }
+    {
+        TimedLaunch t(e, "vec_rollout_kernel", nullptr, true);
+        lobk_vec_rollout(e->stream, e->P.T <= 2, (const DevParams*)e->P_dev, e->S, a);
     }
     HIPCHK(hipGetLastError());
     return LOB_OK;

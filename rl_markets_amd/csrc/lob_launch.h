@@ -1,7 +1,7 @@
-// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is thirteen
+// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is fourteen
 // .hip files built in parallel: lob_engine.hip -- the C ABI's host side and the update / memo / trace kernels --, lob_tu_env.hip,
 // lob_tu_prepass.hip, lob_tu_learn.hip, lob_tu_stats.hip, lob_tu_steplog.hip, lob_tu_vec.hip, lob_tu_vecbook.hip, lob_tu_vechist.hip, lob_tu_snapshot.hip,
-// lob_tu_vecact.hip, lob_tu_vecfeat.hip, lob_tu_vecpeek.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
+// lob_tu_vecact.hip, lob_tu_vecfeat.hip, lob_tu_vecpeek.hip, lob_tu_vecroll.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
 // lob_engine.hip used when it held the launches itself.  Kernels measured and lost (NOTES.md "Round 4") are only compiled with
 // -DLOB_EXPERIMENTS (tools/exp_variants.sh); a product build answers LOB_EXPERIMENTS-only requests with the product kernel.
 #ifndef LOB_LAUNCH_H
@@ -231,6 +231,23 @@ struct PeekSrc {
 };
 // vec_peek_kernel<t2>: n_act * Bpad / 64 one-wave blocks; `t2` as lobk_env's
 void lobk_vec_peek(hipStream_t st, bool t2, const DevParams* Pd, const DevState& S, const PeekSrc& a);
+
+// ---- lob_tu_vecroll.hip ----
+// What lob_vec_rollout (include/lob_engine.h) takes beyond the parameters and the state, which vec_rollout_kernel receives as
+// env_kernel does: the plans' actions [P][H][B], the batch and its size rounded up to whole waves -- block i of the grid is plan
+// i / (Bpad / 64) over the books 64 * (i % (Bpad / 64)) ... --, the discount, the caller's device buffers (plan-major planes) and the
+// engine's workspace for the PnL windows' entries a plan itself has pushed: `shadow` [2][w][n_plans * Bpad] f64, lane
+// p * Bpad + b innermost, null unless the reward reads the windows and 1 < lb_pnl < horizon.
+struct RolloutSrc {
+    const i32* actions;    // [n_plans][horizon][B]
+    i32 B, Bpad;           // books; B rounded up to a multiple of 64
+    i32 n_plans, horizon;
+    f64 gamma;
+    f64* shadow;
+    lob_vec_rollout_out out;
+};
+// vec_rollout_kernel<t2>: n_plans * Bpad / 64 one-wave blocks; `t2` as lobk_env's
+void lobk_vec_rollout(hipStream_t st, bool t2, const DevParams* Pd, const DevState& S, const RolloutSrc& a);
 
 // ---- lob_tu_learn.hip ----
 // learn_q_pair_kernel / learn_q_lane_kernel<algo, vt, tr>: vt = 8 when the state has eight variables (else 0)

@@ -5,7 +5,7 @@
 // device memory -- and nothing of the engine's state moves: the agent half of a step runs on a private copy of the book's scalars
 // (EnvR in an LDS slot, env_load) that is never stored, the market half is the track the pre-pass has written.  The step itself is
 // env_kernel's, call for call: step_prologue, event_loop_fast (two trade slots) or the step_event loop, then the epilogue -- restated
-// below without its stores, because step_epilogue's rm_apply writes the two PnL windows.  Of everything those functions reach, the
+// in lob_peek.h without its stores, because step_epilogue's rm_apply writes the two PnL windows.  Of everything those functions reach, the
 // windows were the only memory written besides EnvCtx::err's flag (a condition the step itself would have raised for that action)
 // and, in -DLOB_PROF builds, the pass clocks.
 #define LOB_TU_SPLIT 1
@@ -14,62 +14,9 @@
 
 #include "lob_internal.h"
 #include "lob_kernels.h"
+#include "lob_peek.h"   // the epilogue without its stores: peek_epilogue, peek_reward
 
 #define LOB_PEEK_BLOCK 64   // one wave per block: 64 consecutive books under one action (env_kernel<64, TM>'s shape)
-
-// rm_apply (lob_env.h) without its stores: the window's running state after the push of `val`, in registers only
-__device__ inline void peek_rm_apply(const RMPtrs& r, RMReg& g, f64 val) {
-    g.sum += val;
-    if (g.cnt < r.w) {
-        g.cnt++;
-        f64 n = (f64)g.cnt;
-        f64 old_mean = g.mean;
-        g.mean += (val - g.mean) / n;
-        g.s += (val - g.mean) * (val - old_mean);
-    } else {
-        f64 n = (f64)(g.cnt + 1);
-        f64 old_mean = g.mean;
-        g.mean += (val - g.mean) / n;
-        g.s += (val - g.mean) * (val - old_mean);
-        g.sum -= g.old;
-        f64 n2 = (f64)g.cnt;
-        f64 old_mean2 = g.mean;
-        g.mean -= (g.old - g.mean) / n2;
-        g.s -= (g.old - g.mean) * (g.old - old_mean2);
-    }
-    g.head = g.slot;
-}
-// rm_std over the registers
-__device__ inline f64 peek_rm_std(const RMReg& g) {
-    f64 v = g.s / (f64)(g.cnt - 1);
-    return v > 0 ? sqrt(v) : 0.0;
-}
-// step_epilogue (lob_env.h) with the two windows kept in `wu` / `wd`
-__device__ inline void peek_epilogue(const EnvCtx& c, EnvR& e, const StepAgg& g, RMReg& wu, RMReg& wd) {
-    e.pnl_step = g.pnl;
-    rm_load(c.S.pnl_ups, c.b, wu); rm_load(c.S.pnl_downs, c.b, wd);
-    rm_prep(c.S.pnl_ups, c.S.B, c.b, wu); rm_prep(c.S.pnl_downs, c.S.B, c.b, wd);
-    peek_rm_apply(c.S.pnl_ups, wu, 0.0 > e.pnl_step ? 0.0 : e.pnl_step);
-    peek_rm_apply(c.S.pnl_downs, wd, fabs(0.0 < e.pnl_step ? 0.0 : e.pnl_step));
-    e.ep_reward += g.r;
-    e.ep_bandh += g.mpm;
-}
-// get_reward (lob_env.h) of the state behind peek_epilogue: LOB_REWARD_NORMED reads the two windows, which here are `wu` / `wd` and
-// not the engine's memory; every other measure reads the book's scalars only
-__device__ inline f64 peek_reward(const EnvCtx& c, const EnvR& e, const RMReg& wu, const RMReg& wd) {
-    if (c.P.reward_measure != LOB_REWARD_NORMED) return get_reward(c, e);
-    const RMPtrs &u_ = c.S.pnl_ups, &d_ = c.S.pnl_downs;
-    f64 r = 0.0;
-    if (!(wu.cnt == u_.w && wd.cnt == d_.w)) r = 0.0;
-    else {
-        f64 u = wu.mean, d = wd.mean, su = peek_rm_std(wu), sd = peek_rm_std(wd);
-        f64 numer = (u * sd - d * su), denom = (su + sd);
-        if (isnan(numer) || isinf(numer)) numer = 0.0;
-        if (isnan(denom) || isinf(denom)) denom = 0.0;
-        r = (fabs(denom) < 1e-5) ? numer : (numer / denom);
-    }
-    return r * 100;
-}
 
 // One lane per (action, book), action-major: block i is the (i / blocks_per_plane)-th action of the mask over the books
 // 64 * (i % blocks_per_plane) ..., so a wave holds 64 consecutive books under ONE action -- env_load's [B] field arrays are read

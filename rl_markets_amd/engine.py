@@ -343,6 +343,17 @@ class Engine:
         refused on a ring-mode stream."""
         self._check(self.lib.lob_vec_peek(self.h, int(mask), C.byref(out)))
 
+    def vec_rollout(self, actions_ptr, n_plans, horizon, gamma, out):
+        """lob_vec_rollout: for each of `n_plans` plans, what `horizon` consecutive vec_step calls would write from the books' present
+        state, the h-th with the actions int32 [n_plans, horizon, B] at the DEVICE address `actions_ptr` -- into the device buffers of
+        `out` (abi.VecRolloutOut: obs f32 [P, B, V] and terminal uint8 [P, B] behind the last step, reward f64 [P, H, B] of every
+        step, stepped int32 [P, B] completed steps, ret f64 [P, B] the rewards discounted by `gamma` in [0, 1]; 0 = not wanted) --
+        and nothing of the engine changes.  An action outside 0 .. 8 skips that step for that book and is not counted by
+        vec_status.  One launch, enqueued on the engine's stream; works after snapshot_restore() and with the step log on; refused
+        on a ring-mode stream.  With reward_measure NORMED and 1 < lb_pnl < horizon the first call (and one that needs more than
+        any before) allocates the engine's workspace, which synchronises the device."""
+        self._check(self.lib.lob_vec_rollout(self.h, C.c_void_p(actions_ptr), int(n_plans), int(horizon), float(gamma), C.byref(out)))
+
     def snapshot_save(self, slot, mask_ptr=None):
         """lob_snapshot_save: the environment state of the books selected by the DEVICE mask at address `mask_ptr` (uint8 [B],
         nonzero selects; None: every book, which (re)starts the slot) into snapshot slot `slot` (0 .. abi.MAX_SNAPSHOTS - 1);

@@ -66,6 +66,12 @@ stay exactly where they are.  One-step expectimax targets under the engine's own
 
 Not available on a ring-mode stream.  A VecEnv that never calls peek() allocates and launches nothing for it.
 
+rollout(plans, gamma) is the same model several steps deep (lob_vec_rollout): the books rolled forward H steps under each of P
+candidate plans per book, int32 [P, H, B] (or [P, H]: the same plan for every book), in one launch -- the reward of every step, the
+observation and terminal behind the last, the steps that completed and the discounted return, as fresh tensors; the books stay
+exactly where they are.  An action of -1 skips that step for that book: plans of unequal length.  Not available on a ring-mode
+stream.  A VecEnv that never calls rollout() allocates and launches nothing for it.
+
 step() reads the actions from the tensor's device memory and writes into five persistent tensors (lob_vec_step,
 include/lob_engine.h): no copy to or from the host and no synchronisation.  The engine runs on a stream of its own; it is made
 to wait for torch's current stream before the call (the actions are ready) and torch's current stream for the engine's after it
@@ -199,6 +205,46 @@ class VecEnv:
         self.eng.vec_peek(mask, self.peek_out)
         cur.wait_stream(self.stream)
         return self.peek_obs, self.peek_reward, self.peek_terminal, self.peek_stepped
+
+    def rollout(self, plans, gamma=1.0):
+        """lob_vec_rollout: multi-step look-ahead under action plans.  plans: a contiguous int32 CUDA tensor [P, H, B] on the
+        engine's device, plans[p, h, b] the action of plan p at step h for book b (1 <= P <= abi.MAX_ROLLOUT_PLANS, 1 <= H <=
+        abi.MAX_ROLLOUT_STEPS); [P, H]: the same plan for every book.  Returns fresh tensors (obs f32 [P, B, V], reward f64
+        [P, H, B], terminal uint8 [P, B], stepped int32 [P, B], ret f64 [P, B]): what H consecutive step() calls would return from
+        here under plan p -- every step's reward, obs and terminal behind the last step, the number of steps that completed, and
+        ret = sum over h of gamma ** h * reward[p, h] (0 <= gamma <= 1).  A book that is over gives reward 0 and keeps its last
+        observation; an action outside 0 .. 8 skips that step for that book and is not counted by status().  Nothing of the
+        environment changes.  Random-shooting model-predictive control with the engine's own values at the leaves:
+
+            plans = torch.randint(0, 9, (P, H, B), dtype=torch.int32, device=dev)
+            o, r, t, n, ret = env.rollout(plans, gamma)
+            tail = env.q_values(o.view(P * B, V)).view(P, B, 9).max(-1).values
+            best = (ret + gamma ** H * tail * (t == 0)).argmax(0)
+            env.step(plans[best, 0, torch.arange(B, device=dev)].contiguous())
+        """
+        if (not isinstance(plans, torch.Tensor) or plans.dtype != torch.int32 or not plans.is_cuda or plans.device != self.device
+                or plans.dim() not in (2, 3) or (plans.dim() == 3 and plans.shape[2] != self.B) or not plans.is_contiguous()
+                or not 1 <= plans.shape[0] <= abi.MAX_ROLLOUT_PLANS or not 1 <= plans.shape[1] <= abi.MAX_ROLLOUT_STEPS):
+            raise ValueError("VecEnv.rollout: plans must be a contiguous int32 CUDA tensor of shape (P, H, %d) or (P, H) on the engine's device, "
+                             "1 <= P <= %d, 1 <= H <= %d" % (self.B, abi.MAX_ROLLOUT_PLANS, abi.MAX_ROLLOUT_STEPS))
+        gamma = float(gamma)
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError("VecEnv.rollout: gamma must lie in [0, 1]")
+        P, H = int(plans.shape[0]), int(plans.shape[1])
+        if plans.dim() == 2:
+            plans = plans.unsqueeze(2).expand(P, H, self.B).contiguous()
+        obs = torch.empty((P, self.B, self.V), dtype=torch.float32, device=self.device)
+        reward = torch.empty((P, H, self.B), dtype=torch.float64, device=self.device)
+        terminal = torch.empty((P, self.B), dtype=torch.uint8, device=self.device)
+        stepped = torch.empty((P, self.B), dtype=torch.int32, device=self.device)
+        ret = torch.empty((P, self.B), dtype=torch.float64, device=self.device)
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)      # the plans are ready
+        self.eng.vec_rollout(plans.data_ptr(), P, H, gamma,
+                             abi.VecRolloutOut(obs.data_ptr(), reward.data_ptr(), terminal.data_ptr(), stepped.data_ptr(), ret.data_ptr()))
+        cur.wait_stream(self.stream)
+        plans.record_stream(cur)          # (as step() does with the actions)
+        return obs, reward, terminal, stepped, ret
 
     def q_values(self, vars):
         """lob_vec_q: Q(s, .) under the engine's weights (theta; book 0's under private theta) for n free-standing states, f32 [n, V]
