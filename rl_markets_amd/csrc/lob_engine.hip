@@ -1,8 +1,8 @@
-// Host side of the C ABI (include/lob_engine.h): device memory management,
-// kernel launches on one HIP stream, HIP-event kernel timing.  gfx950 only;
-// there is no CPU execution path in this file.  (One of the library's six translation units, lob_launch.h: the environment,
-// pre-pass, fast learner, episode-statistics and step-log kernels are compiled in lob_tu_env.hip / lob_tu_prepass.hip / lob_tu_learn.hip /
-// lob_tu_stats.hip / lob_tu_steplog.hip.)
+// Host side of the C ABI (include/lob_engine.h), the part that launches kernels of this unit by name: the engine object's life
+// (lob_create / lob_destroy / lob_reset), the step pipeline, the weights and both weight exchanges, kernel timing, the
+// diagnostics that launch.  gfx950 only; there is no CPU execution path in this file.  (One of the library's fourteen units with
+// kernels, lob_launch.h -- the update, memo and trace kernels are compiled here --; the streams, the vector env with the
+// snapshots, and the read-backs and logs are host-only units of their own, lob_tu_host_*.hip, over lob_engine_impl.h.)
 #define LOB_TU_SPLIT 1
 #define LOB_TU_MAIN 1
 #include <hip/hip_runtime.h>
@@ -13,13 +13,8 @@
 
 #include <algorithm>
 #include <climits>
-#include <condition_variable>
 #include <initializer_list>
-#include <map>
-#include <mutex>
 #include <string>
-#include <system_error>
-#include <thread>
 #include <vector>
 
 #include "lob_internal.h"
@@ -27,215 +22,7 @@
 #include "lob_kernels.h"
 #include "lob_launch.h"
 
-#define HIPCHK(expr)                                                                         \
-    do {                                                                                     \
-        hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess) {                                                              \
-            lob_set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                \
-            return LOB_EHIP;                                                                 \
-        }                                                                                    \
-    } while (0)
-
-// parameters and state of the kernels that take them by pointer (lob_state.h LOB_PS_ARGS): their device-resident copies
-#define LOB_PS(e) (const DevParams*)(e)->P_dev, (e)->S.self
-
-#define LOB_HINT_RING 64
-#define LOB_HINT_LAG 16
-#define LOB_HINT_EVERY 8   /* the count goes to host memory in every 8th learner step only: the store costs the kernel that makes it 3.5 us */
-
-struct KTimer {
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
-    double total_ms = 0.0;
-    int64_t launches = 0;
-};
-
-// Runtime switches (INTEGRATION.md §6 says what each does), read once by read_switches at lob_create.  Honoured by every build:
-// the A/B switches of first-class paths that the parity tests force on or off at sizes that would not select them, the table sizes
-// the tests squeeze, the track ring, the upload's pieces and the exchange's first count.  The switches of variants measured and
-// lost, and of timing experiments, only by a -DLOB_EXPERIMENTS build (tools/exp_variants.sh; NOTES.md): read_switches leaves
-// them at their defaults otherwise.  (LOB_DENSE_EXCHANGE is lob_comm.cpp's.)
-struct Switches {
-    bool no_memo = false, no_carry = false, no_combine = false, light = true, force_fuse_act = false, t_light = true, no_fuse = false;
-    bool q_pair = true, dq_pair = true, trace_lanes_off = false, acc_fuse = true, rest_merge = true, acc_dense = true;
-    int q_lanes = -1, force_general = -1;  // -1: by batch size / by the learn kernels' hand-back count
-    int env_lanes = 0, env16_max = 4096;   // env_lanes 0: by batch size
-    int acc_batches = 0, acc_shift = -1;   // 0 / -1: by algorithm, batch size and epsilon
-    int cb_slots = 0, ow_slots = 0, amb_cap = 0, cbd_ids = 0;  // 0: by size
-    int track_ring = 4096, track_refill = 64;
-    long long upload_piece_recs = 0, spx_count = 0;  // 0: 64 MB pieces / by table size
-    bool upload_pinned = true;
-    // (-DLOB_EXPERIMENTS builds only)
-    bool fuse_act = true, inline_general = true, env_step = true, prepass_roles = false, sarsa_lanes_off = false, dq_fast_off = false;
-    bool rest_side = true, acc_block = true, exp_learn_first = false, no_hint = false;
-    int env_step_lanes = 64, reset_lanes = 64, n_groups = 1, acc_reps = 0, ts_lds = 0, ts_grid = 0;  // acc_reps 0: by path
-};
-
-// The kernel paths fixed for the engine's life, by plan_paths from the parameters, the batch, the CU count and the switches.
-// DevParams carries memo / combine / carry_verdicts / sarsa_lanes from here; run_steps takes every other fixed choice from here.
-struct EnginePlan {
-    int groups = 1;             // book groups of the step pipeline
-    bool combine = false, memo = false, carry_verdicts = false, sarsa_lanes = false;  // (DevParams)
-    bool q_lanes = false;       // Q(s', .) + TD error with lanes per book, else a wave per book (learn_q_fast_kernel)
-    bool q_pair = false;        // ... two per book (learn_q_pair_kernel), else one (learn_q_lane_kernel)
-    bool t_light = false;       // Q(lambda) / double Q: the light trace step for the books that keep no older generation
-    bool fuse = false;          // ... inside the lane learn kernel, else trace_light_kernel
-    bool fused_act_ok = false;  // the action selection may ride in the env kernel (fast-path learner steps on live hit lists)
-    bool env_step = false, half_waves = false, env16 = false;  // ... in env_step_kernel (else env_kernel<64, TM, 1>): 32 lanes / 16 lanes per book
-    bool inline_ok = false;     // ... which may serve the books without a hit list itself
-    int env_lanes = 64;         // books per env_kernel wave
-    bool acc_block_ok = false;  // the update may sum per block (StepPlan::acc_blocked), ...
-    bool dense_ids = false;     // ... by the slots' dense ids
-    bool acc_fuse_ok = false;   // updates may be added to their slots by the learn / trace kernels (StepPlan::acc_fused)
-    bool rest_side_ok = false;  // learn_q_rest_kernel may run on the second stream
-    bool learn_first = false;   // (experiment) SARSA(lambda)'s learn kernels in front of its trace kernels
-};
-
-struct lob_engine {
-    int device = 0;
-    int B = 0;
-    lob_params params;
-    Switches sw;
-    EnginePlan plan;
-    DevParams P;
-    DevParams* P_dev = nullptr;  // device copy for the lane-per-book kernels
-    DevState S;
-    // The device-resident copy of S, at one address for the engine's lifetime (S.self): kernels that take the state by POINTER read
-    // the fields they need where they need them, through the scalar cache -- 1 728 bytes of by-value kernel arguments are loaded at
-    // the kernel's entry, live across all of it and cost env_step_kernel 104 spilled scalar registers + 160 vector registers parked
-    // in AGPRs (round 6).  Kept up by sync_state() before every launch sequence, which uploads the two words a learner step
-    // changes (cb_par, cb_dense_on) as 0; the claims read them through the pointer (cb_claim_finish), so every learner step
-    // publishes them before its first claim (publish_step_words).
-    DevState* S_dev = nullptr;
-    DevState S_pushed;
-    hipStream_t stream = nullptr;   // main stream (all API calls)
-    hipStream_t stream2 = nullptr;  // second book group of the step pipeline
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_stagger = nullptr;
-    hipEvent_t ev_rest_go = nullptr, ev_rest_done = nullptr;  // learn_q_rest_kernel on stream2 beside the trace kernels
-    long long flow[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // lob_debug_flow: learner steps by the shape of their update / action selection (see there)
-    long long hint_reads = 0, hint_misses = 0;  // lob_debug_hint: learner steps that read a hint word / found it still unwritten after the spin limit
-    bool dense_ever = false;    // the dense sums have been on at some step: slots may hold dense ids (apply_kernel frees them with their slots)
-    // learn_q_rest_kernel reports its list's length (the books the lane learn kernels handed back) through host-mapped memory:
-    // a ring of LOB_HINT_RING words, one per learner step, each with an event recorded behind the kernel that writes it.  The
-    // step launched now reads the word of LOB_HINT_LAG steps ago after waiting for THAT event (long past, unless the host is
-    // more than LOB_HINT_LAG steps ahead of the device -- then it waits: the device still has that many steps queued), so which
-    // path a step takes is a function of the run, not of the host's timing.  The first LOB_HINT_LAG steps after
-    // lob_reset / lob_theta_set read 0.  A weight exchange (lob_delta_apply / lob_delta_sparse_apply) does NOT void the counts:
-    // it runs every 64 steps, the written set only grows by the union of the ranks', and which books have no usable hit list
-    // hardly changes -- voiding them would send a quarter of a dense-theta run's steps down the slower path.
-    u64* rest_hint = nullptr;   // word = (step tag) << 32 | count: the host checks the tag, so it never reads a word the device has not written yet
-    u64* rest_hint_dev = nullptr;
-    hipEvent_t hint_ev[LOB_HINT_RING] = {};
-    long long hint_step = 0;    // learner steps (fast path) since the hints were last void
-    unsigned long long hint_serial = 0;  // launches of learn_q_rest_kernel since lob_create (the tag of a ring word)
-    uint32_t hint_tags[LOB_HINT_RING] = {};
-    int hint_now = 0;           // the hint this step goes by (run_steps)
-    int rest_recent = 0;        // steps left to keep the launch on the second stream after the last non-empty list seen
-    int reg_apar = 0;   // which of the two lists of newly ambiguous indices this step's registry blocks fill (trace_lane_kernel's launch) and its scan blocks read (apply_kernel's)
-    int td_parity = 0;
-    int step_id = 0;            // stamps the memo claims of one step
-    int list_par = 0;           // parity of the fast path's work lists
-    int last_par = 0;           // `par` of the most recent step (its memo list is the current one)
-    int n_cus = 256;            // compute units: the persistent learner kernels run one block on each
-    bool chunked = false;       // the loaded stream is longer than the ring
-    int steps_since_fill = 0;
-    uint64_t theta_ver = 1;     // bumped whenever theta changes: memo records carry the version they were computed under
-    bool half_open = false;     // between lob_td_step_begin and lob_td_step_end
-    bool hits_ok = false;       // the previous call was a fast-path learner step and nothing has touched weights, maps or states since:
-                                // the hit lists its learn kernel left are those of the States the next step acts on (act_light_kernel)
-    int steps_on_lists = 0;     // fused steps since the hit lists were last void
-    std::vector<void*> allocs;
-    // sparse weight exchange (lob_delta_sparse_*): the ranks' gathered maps, their union, per-block counts / offsets, the packed deltas
-    uint32_t* spx_gather = nullptr;
-    int spx_world = 0;
-    uint32_t* spx_union = nullptr;
-    i32* spx_block_cnt = nullptr;
-    i64* spx_block_off = nullptr;
-    i64* spx_total = nullptr;
-    f64* spx_buf = nullptr;
-    int64_t spx_cap = 0, spx_count = 0;
-    // The exchange without a host synchronisation: the packed vector's length is a host argument of the
-    // collective, and the union's true size is only known on the device.  So the ranks exchange a FIXED count -- spx_fixed, the
-    // same on every rank because it is a function of the union sizes of the exchanges before, which are the same on every rank --
-    // with the tail behind the union zero-filled, and every exchange leaves its union's size in pinned host memory behind an event
-    // that the NEXT exchange (64 steps later: long past) reads.  The union only grows, ever more slowly (the written set saturates):
-    // an exchange goes without a synchronisation when the last size + twice the last increase still fits spx_fixed; the first two
-    // exchanges, and any whose prediction does not fit, take the exact count with a synchronisation and set spx_fixed to at least
-    // twice it.  A union that outgrows the count anyway (its growth more than doubled from one interval to the next) loses nothing:
-    // the entries beyond it keep theta - theta_sync and travel with the next exchange (counted: lob_debug_exchange; the parity
-    // tests of the exchange assert that it never happens in them).
-    i64* spx_total_host = nullptr;   // pinned
-    hipEvent_t spx_ev = nullptr;
-    int64_t spx_fixed = 1 << 18, spx_last_total = -1, spx_prev_total = -1;
-    bool spx_ev_pending = false;
-    long long spx_nosync = 0, spx_synced = 0, spx_overflows = 0;
-    uint32_t* rnd_dev = nullptr;
-    uint32_t* records_dev = nullptr;
-    // The NEXT episode's streams, handed over while the current episode runs (lob_stage_events): a second record buffer filled by
-    // a host thread through a stream of its own -- validation, pinned staging, DMA, repack, none of it on the engine's stream --
-    // and adopted by the lob_reset that follows.  The reference loads a fresh day before every episode (src/main.cpp:53-55).
-    size_t records_bytes = 0, track_bytes = 0;   // sizes of records_dev / track_dev (set_records re-uses buffers of the right size)
-    uint32_t* records_next = nullptr;
-    hipStream_t stream_up = nullptr;
-    std::thread stage_thread;
-    bool stage_active = false;      // a hand-over has been started and not adopted / waited for yet
-    int stage_rc = LOB_OK;
-    std::string stage_err;
-    i64* phase_dev = nullptr;  // replayed stream: first record of every book's window
-    // Day library (lob_load_days): the days back to back in records_dev, their tables, and two sets of every book's
-    // (first record, length, day) -- the set the current episode plays and the one a selection writes for the next
-    bool lib = false;
-    int lib_days = 0;
-    i64* day_first_dev = nullptr;   // [lib_days] first record of each day
-    i32* day_len_dev = nullptr;     // [lib_days] its events
-    uint32_t* day_rng = nullptr;    // [B] each book's minstd_rand0 state (persists across draws)
-    i32* day_explicit = nullptr;    // [B] lob_days_set's days on the device
-    i32* day_explicit_host = nullptr;  // [B] pinned: the host side of that copy
-    hipEvent_t day_copied = nullptr;   // the copy out of day_explicit_host has been done
-    i64* lib_phase[2] = {nullptr, nullptr};
-    i32* lib_len[2] = {nullptr, nullptr};
-    i32* lib_day[2] = {nullptr, nullptr};
-    int lib_cur = -1;           // the set the current episode plays (-1: no episode on the library yet)
-    bool lib_pending = false;   // a selection waits for the next lob_reset (in set lib_cur ^ 1, or 0)
-    Track* track_dev = nullptr;
-    i32* actions_dev = nullptr;
-    f64* roll_ws = nullptr;     // lob_vec_rollout: the PnL windows' entries the plans push (lob_launch.h RolloutSrc::shadow), made by the first
-    size_t roll_ws_elems = 0;   // call that needs it, grown when a later call needs more, never per call
-    u64* vec_bad = nullptr;     // lob_vec_step: actions out of range since the last lob_vec_status / lob_reset (one device word)
-    i32* vec_upd_tag = nullptr; // lob_vec_update: the number of the last launch that wrote a weight (one device word; lob_launch.h VecFeatSrc)
-    i32 vec_upd_launch = 0;     // ... and the number of the last launch (never 0 once used)
-    uint32_t vec_terms[27] = {0};   // lob_vec_terms: the 27 action terms mod M, as uploaded behind the hash table
-    i64* cnt_sum = nullptr;     // the striped device counters added up (read_counters)
-    lob_book_dump* dump_dev = nullptr;
-    int dump_cap = 0;
-    lob_episode_record* stats_dev = nullptr;   // lob_episode_stats: [stats_cap] result records, then the blocks' partial records
-    size_t stats_cap = 0;
-    // lob_step_log_*: the device log of the selected books' profit-log rows (lob_tu_steplog.hip), all of it the engine's own
-    lob_step_row* slog_rows = nullptr;    // [slog_cap][slog_n], step-major
-    i32* slog_cnt = nullptr;              // [2][slog_n]: stored rows, lost rows
-    i32* slog_sel = nullptr;              // [slog_n] local book indices (null: every book)
-    int slog_n = 0, slog_cap = 0;         // slog_n == 0: the log is off
-    bool slog_armed = false;              // a lob_reset has come since lob_step_log_enable: the steps record
-    lob_step_row* slog_stage = nullptr;   // lob_step_log_read's book-major staging buffer, grown like dump_dev
-    size_t slog_stage_cap = 0;
-    // lob_snapshot_*: the slot buffers (one allocation each, made by the slot's first save), whether each holds a full save of the
-    // current episode, the descriptor table of the saved arrays (lob_launch.h SnapArgs; built with the first save) and the flag
-    // that keeps the learner calls off a restored batch until the next lob_reset
-    void* snap_buf[LOB_MAX_SNAPSHOTS] = {nullptr, nullptr, nullptr, nullptr};
-    bool snap_valid[LOB_MAX_SNAPSHOTS] = {false, false, false, false};
-    void* snap_tab = nullptr;
-    SnapArgs snap_args;
-    size_t snap_bytes = 0;
-    bool restored = false;
-    bool have_events = false, was_reset = false;
-    bool episode_open = false;  // a pre-pass ran and its window sums have not been rolled back to the stop point yet
-    bool model_log = false;     // lob_model_log_enable: the step sums |delta| (td_stats_kernel)
-    bool timing = false;
-    int timing_period = 1;  // kernels of every n-th step are timed (two event records per launch are not free: 9 % at n = 1)
-    std::map<std::string, KTimer> timers;
-    std::vector<hipEvent_t> event_pool;
-    // lob_debug_launches (below, beside lob_debug_flow): launches of kernels that share a timer name
-    int64_t launched[6] = {0, 0, 0, 0, 0, 0};
-};
+#include "lob_engine_impl.h"
 
 namespace {
 
@@ -262,109 +49,8 @@ void make_rndseq(uint32_t* t) {
     }
 }
 
-template <class T> int dev_alloc(lob_engine* e, T** p, size_t count) {
-    void* q = nullptr;
-    size_t bytes = count * sizeof(T);
-    if (bytes == 0) bytes = sizeof(T);
-    hipError_t err = hipMalloc(&q, bytes);
-    if (err != hipSuccess) {
-        lob_set_error(std::string("hipMalloc failed: ") + hipGetErrorString(err));
-        return LOB_ENOMEM;
-    }
-    err = hipMemsetAsync(q, 0, bytes, e->stream);
-    if (err != hipSuccess) { lob_set_error("hipMemset failed"); return LOB_EHIP; }
-    e->allocs.push_back(q);
-    *p = (T*)q;
-    return LOB_OK;
-}
-
-template <class T> int dev_alloc(lob_engine* e, GP<T>* p, size_t count) { return dev_alloc(e, &p->p, count); }
-
-// The device copy of DevState follows the host's (rare: a stream loaded, the exchange's buffers allocated, model_log switched on).
-// (Copied byte for byte, so that memcmp compares exactly the bytes that were uploaded, padding included.)
-int sync_state(lob_engine* e) {
-    DevState now;
-    memcpy(&now, &e->S, sizeof(DevState));
-    now.cb_par = 0;
-    now.cb_dense_on = 0;
-    now.self = e->S_dev;
-    if (memcmp(&now, &e->S_pushed, sizeof(DevState)) == 0) return LOB_OK;
-    if (hipMemcpyAsync(e->S_dev, &now, sizeof(DevState), hipMemcpyHostToDevice, e->stream) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) {
-        lob_set_error("state upload failed");
-        return LOB_EHIP;
-    }
-    memcpy(&e->S_pushed, &now, sizeof(DevState));
-    return LOB_OK;
-}
-int push_params(lob_engine* e) {
-    if (hipMemcpyAsync(e->P_dev, &e->P, sizeof(DevParams), hipMemcpyHostToDevice, e->stream) != hipSuccess) { lob_set_error("param upload failed"); return LOB_EHIP; }
-    return LOB_OK;
-}
-
 int grid_lanes(int B) { return (B + 255) / 256; }
 int grid_waves(int B) { return (B + LOB_WAVES_PER_BLOCK - 1) / LOB_WAVES_PER_BLOCK; }
-
-struct TimedLaunch {
-    lob_engine* e;
-    KTimer* t = nullptr;
-    hipEvent_t a = nullptr, b = nullptr;
-    hipStream_t st;
-    // `always`: kernels that do not run every step (reset, weight exchange, ring refill) are timed whenever timing is on
-    TimedLaunch(lob_engine* e_, const char* name, hipStream_t s = nullptr, bool always = false) : e(e_), st(s ? s : e_->stream) {
-        if (!e->timing || (!always && e->timing_period > 1 && e->step_id % e->timing_period != 0)) return;
-        t = &e->timers[name];
-        auto get = [&]() {
-            hipEvent_t ev;
-            if (!e->event_pool.empty()) { ev = e->event_pool.back(); e->event_pool.pop_back(); }
-            else hipEventCreateWithFlags(&ev, hipEventDisableSystemFence);
-            return ev;
-        };
-        a = get();
-        b = get();
-        hipEventRecord(a, st);
-    }
-    ~TimedLaunch() {
-        if (!t) return;
-        hipEventRecord(b, st);
-        t->pending.push_back({a, b});
-    }
-};
-
-void drain_timers(lob_engine* e) {
-    for (auto& kv : e->timers) {
-        for (auto& pr : kv.second.pending) {
-            hipEventSynchronize(pr.second);
-            float ms = 0;
-            hipEventElapsedTime(&ms, pr.first, pr.second);
-            kv.second.total_ms += ms;
-            kv.second.launches++;
-            e->event_pool.push_back(pr.first);
-            e->event_pool.push_back(pr.second);
-        }
-        kv.second.pending.clear();
-    }
-}
-
-// LOB_EDATA and its message for a non-zero device error word
-static int device_error_rc(i32 flag) {
-    if (flag) {
-        std::string m = "device reported a condition on which the reference throws:";
-        if (flag & LOB_ERR_BAD_ORDER_PRICE) m += " [order price <= 0]";
-        if (flag & LOB_ERR_BAD_LEVEL) m += " [level price/volume <= 0]";
-        if (flag & LOB_ERR_UNDEF_PRICE) m += " [undefined book price]";
-        if (flag & LOB_ERR_TRADE_OVERFLOW) m += " [more trade price levels in one event than max_trades]";
-        if (flag & LOB_ERR_TRACK_UNDERRUN) m += " [market-track ring underrun: raise LOB_TRACK_RING or lower LOB_TRACK_REFILL]";
-        lob_set_error(m);
-        return LOB_EDATA;
-    }
-    return LOB_OK;
-}
-int check_device_errors(lob_engine* e) {
-    i32 flag = 0;
-    HIPCHK(hipMemcpyAsync(&flag, e->S.error_flag, sizeof flag, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return device_error_rc(flag);
-}
 
 // The shapes of the switches' values: set at all, to anything; "=0" / "=1" (the first character); a number in [lo, hi]; one of
 // {...}; a power of two in [lo, hi].  Anything else leaves the default.
@@ -447,6 +133,126 @@ EnginePlan plan_paths(const DevParams& P, int B, int n_cus, const Switches& sw) 
 }
 
 }  // namespace
+
+namespace lob {
+
+// The device copy of DevState follows the host's (rare: a stream loaded, the exchange's buffers allocated, model_log switched on).
+// (Copied byte for byte, so that memcmp compares exactly the bytes that were uploaded, padding included.)
+int sync_state(lob_engine* e) {
+    DevState now;
+    memcpy(&now, &e->S, sizeof(DevState));
+    now.cb_par = 0;
+    now.cb_dense_on = 0;
+    now.self = e->S_dev;
+    if (memcmp(&now, &e->S_pushed, sizeof(DevState)) == 0) return LOB_OK;
+    if (hipMemcpyAsync(e->S_dev, &now, sizeof(DevState), hipMemcpyHostToDevice, e->stream) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) {
+        lob_set_error("state upload failed");
+        return LOB_EHIP;
+    }
+    memcpy(&e->S_pushed, &now, sizeof(DevState));
+    return LOB_OK;
+}
+int push_params(lob_engine* e) {
+    if (hipMemcpyAsync(e->P_dev, &e->P, sizeof(DevParams), hipMemcpyHostToDevice, e->stream) != hipSuccess) { lob_set_error("param upload failed"); return LOB_EHIP; }
+    return LOB_OK;
+}
+
+void drain_timers(lob_engine* e) {
+    for (auto& kv : e->timers) {
+        for (auto& pr : kv.second.pending) {
+            hipEventSynchronize(pr.second);
+            float ms = 0;
+            hipEventElapsedTime(&ms, pr.first, pr.second);
+            kv.second.total_ms += ms;
+            kv.second.launches++;
+            e->event_pool.push_back(pr.first);
+            e->event_pool.push_back(pr.second);
+        }
+        kv.second.pending.clear();
+    }
+}
+
+// LOB_EDATA and its message for a non-zero device error word
+int device_error_rc(i32 flag) {
+    if (flag) {
+        std::string m = "device reported a condition on which the reference throws:";
+        if (flag & LOB_ERR_BAD_ORDER_PRICE) m += " [order price <= 0]";
+        if (flag & LOB_ERR_BAD_LEVEL) m += " [level price/volume <= 0]";
+        if (flag & LOB_ERR_UNDEF_PRICE) m += " [undefined book price]";
+        if (flag & LOB_ERR_TRADE_OVERFLOW) m += " [more trade price levels in one event than max_trades]";
+        if (flag & LOB_ERR_TRACK_UNDERRUN) m += " [market-track ring underrun: raise LOB_TRACK_RING or lower LOB_TRACK_REFILL]";
+        lob_set_error(m);
+        return LOB_EDATA;
+    }
+    return LOB_OK;
+}
+int check_device_errors(lob_engine* e) {
+    i32 flag = 0;
+    HIPCHK(hipMemcpyAsync(&flag, e->S.error_flag, sizeof flag, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return device_error_rc(flag);
+}
+
+int finalize_episode(lob_engine* e) {
+    if (!e->episode_open) return LOB_OK;
+    lobk_finalize(e->stream, e->P.T <= 2, (const DevParams*)e->P_dev, e->S);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->episode_open = false;
+    return LOB_OK;
+}
+
+// env_kernel with EnginePlan::env_lanes books per wave
+void launch_env(lob_engine* e, hipStream_t st, const i32* actions, int count_updates, int b0, int nb, int par) {
+    lobk_env(st, e->plan.env_lanes, e->P.T <= 2, (const DevParams*)e->P_dev, e->S, actions, count_updates, b0, nb, e->step_id, par);
+}
+// Long streams: let the pre-pass run on every `track_refill` steps (lob_kernels.h prepass_extend_kernel)
+void maybe_refill_track(lob_engine* e) {
+    if (!e->chunked || ++e->steps_since_fill < e->sw.track_refill) return;
+    e->steps_since_fill = 0;
+    TimedLaunch t(e, "prepass_extend_kernel", nullptr, true);
+    lobk_prepass_extend(e->stream, e->P.T <= 2, e->sw.prepass_roles, (const DevParams*)e->P_dev, e->S);
+}
+// S0 of every group-0 triple on this step's list (lob_kernels.h memo_kernel): `which` 0 = for learn_kernel
+// (theta_t), 1 = for the next act_kernel (after the update)
+void launch_memo(lob_engine* e, int par, int which, int reset_lpar) {
+    TimedLaunch t(e, "memo_kernel");
+    hipLaunchKernelGGL(memo_kernel, dim3(256), dim3(256), 0, e->stream, e->P, e->S, (const uint32_t*)e->rnd_dev, par, which, (u64)e->theta_ver, reset_lpar);
+}
+
+// The step log's row of every selected book that has just completed a step (lob_tu_steplog.hip step_log_kernel): on the main stream
+// behind the step's last kernel; not launched while the log is off or waits for its first lob_reset.
+void launch_step_log(lob_engine* e) {
+    if (!e->slog_armed) return;
+    TimedLaunch t(e, "step_log_kernel");
+    StepLogSrc s;
+    s.done = e->S.done; s.time_ms = e->S.time_ms; s.rec_cur = e->S.rec_cur; s.last_action = e->S.last_action;
+    s.ask_level = e->S.ask_level; s.bid_level = e->S.bid_level; s.total_ticks = e->S.total_ticks;
+    s.position = e->S.position;
+    s.ask_quote = e->S.ask_quote; s.bid_quote = e->S.bid_quote; s.pnl_step = e->S.pnl_step;
+    s.ep_pnl = e->S.ep_pnl; s.ep_bandh = e->S.ep_bandh; s.ep_reward = e->S.ep_reward;
+    s.records = e->S.records; s.rec_phase = e->S.rec_phase;
+    s.n_events = e->S.n_events; s.Wd = e->P.Wd; s.w_ask0 = drec_ask_px(e->P.D, e->P.T); s.w_bid0 = drec_bid_px(e->P.D, e->P.T);
+    s.sel = e->slog_sel; s.n_sel = e->slog_n; s.cap = e->slog_cap;
+    s.rows = e->slog_rows; s.n_rows = e->slog_cnt; s.n_lost = e->slog_cnt + e->slog_n;
+    lobk_step_log(e->stream, s);
+}
+
+// The one check of the engine's state in front of an entry point (lob_engine_impl.h: the bits, and which call asks for which)
+int guard(lob_engine* e, const char* who, unsigned needs) {
+    if (!e) return LOB_EINVAL;
+    const char* why = nullptr;
+    if ((needs & RESET) && !e->was_reset) why = ": call lob_reset first";
+    else if ((needs & WHOLE_STEP) && e->half_open) why = ": a learner step is half done (lob_td_step_begin without lob_td_step_end)";
+    else if ((needs & NOT_RESTORED) && e->restored) why = ": books were put back by lob_snapshot_restore in this episode; the learner runs again after the next lob_reset";
+    else if ((needs & NO_RING) && e->chunked) why = ": the market track of this stream is a ring (longer than LOB_TRACK_RING events)";
+    else if ((needs & NO_RING_BACK) && e->chunked) why = ": the market track of this stream is a ring (longer than LOB_TRACK_RING events): entries before the cursor are gone, no earlier state can be served";
+    if (!why) return LOB_OK;
+    lob_set_error(std::string(who) + why);
+    return LOB_ESTATE;
+}
+
+}  // namespace lob
 
 extern "C" {
 
@@ -766,31 +572,6 @@ int lob_create(const lob_params* p, int32_t n_books, int32_t device, lob_engine*
     return LOB_OK;
 }
 
-// the day library's tables and per-book sets (set_records, lob_destroy)
-static void free_days(lob_engine* e) {
-    if (e->day_copied) hipEventSynchronize(e->day_copied);   // (the pinned buffer may still be read by a copy in flight)
-    for (void* p : {(void*)e->day_first_dev, (void*)e->day_len_dev, (void*)e->day_rng, (void*)e->day_explicit, (void*)e->lib_phase[0],
-                    (void*)e->lib_phase[1], (void*)e->lib_len[0], (void*)e->lib_len[1], (void*)e->lib_day[0], (void*)e->lib_day[1]})
-        if (p) hipFree(p);
-    if (e->day_explicit_host) hipHostFree(e->day_explicit_host);
-    if (e->day_copied) hipEventDestroy(e->day_copied);
-    e->day_first_dev = nullptr; e->day_len_dev = nullptr; e->day_rng = nullptr; e->day_explicit = nullptr; e->day_explicit_host = nullptr;
-    e->day_copied = nullptr;
-    for (int i = 0; i < 2; i++) { e->lib_phase[i] = nullptr; e->lib_len[i] = nullptr; e->lib_day[i] = nullptr; }
-    e->lib = false;
-    e->lib_days = 0;
-    e->lib_cur = -1;
-    e->lib_pending = false;
-}
-
-static void step_log_free(lob_engine* e) {
-    if (e->slog_rows) hipFree(e->slog_rows);
-    if (e->slog_cnt) hipFree(e->slog_cnt);
-    if (e->slog_sel) hipFree(e->slog_sel);
-    e->slog_rows = nullptr; e->slog_cnt = nullptr; e->slog_sel = nullptr;
-    e->slog_n = e->slog_cap = 0;
-    e->slog_armed = false;
-}
 void lob_destroy(lob_engine* e) {
     if (!e) return;
     hipSetDevice(e->device);
@@ -814,14 +595,14 @@ void lob_destroy(lob_engine* e) {
     if (e->phase_dev) hipFree(e->phase_dev);
     free_days(e);
     if (e->track_dev) hipFree(e->track_dev);
-    if (e->dump_dev) hipFree(e->dump_dev);
-    if (e->stats_dev) hipFree(e->stats_dev);
+    e->dump.release();
+    e->stats.release();
     step_log_free(e);
-    if (e->slog_stage) hipFree(e->slog_stage);
-    for (void* p : e->snap_buf) if (p) hipFree(p);
+    e->slog_stage.release();
+    for (auto& b : e->snap_buf) b.release();
     if (e->snap_tab) hipFree(e->snap_tab);
-    if (e->roll_ws) hipFree(e->roll_ws);
-    if (e->spx_gather) hipFree(e->spx_gather);
+    e->roll_ws.release();
+    e->spx_gather.release();
     if (e->spx_ev) hipEventDestroy(e->spx_ev);
     if (e->spx_total_host) hipHostFree(e->spx_total_host);
     if (e->stream) hipStreamDestroy(e->stream);
@@ -867,428 +648,6 @@ static int theta_random_init(lob_engine* e) {
     return LOB_OK;
 }
 
-static int finalize_episode(lob_engine* e) {
-    if (!e->episode_open) return LOB_OK;
-    lobk_finalize(e->stream, e->P.T <= 2, (const DevParams*)e->P_dev, e->S);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(e->stream));
-    e->episode_open = false;
-    return LOB_OK;
-}
-
-static int stage_join(lob_engine* e);
-// n_rows: records to allocate (B * n_events for per-book streams, the stream length for a replayed one)
-static int set_records(lob_engine* e, int32_t n_events, size_t n_rows) {
-    // (the TickStatistics counters of a book are 32-bit like the reference's ints, lob_state.h tick_ab / tick_pos / tick_both: one count
-    // per agent step, at most one agent step per event, n_events < 2^31 -- a recorded day of millions of rows is fine)
-    { int rc = finalize_episode(e); if (rc) return rc; }  // needs the old stream
-    if (e->stage_active) { (void)stage_join(e); e->stage_active = false; }   // (a staged stream is void once another one is loaded)
-    if (e->records_next) { hipFree(e->records_next); e->records_next = nullptr; }
-    // the old stream is gone from here on, whatever happens below: no kernel may see a freed pointer
-    e->have_events = false;
-    e->was_reset = false;
-    e->S.records = nullptr;
-    e->S.track = nullptr;
-    e->S.rec_phase = nullptr;
-    e->S.rec_len = nullptr;
-    e->S.n_events = 0;
-    if (e->phase_dev) { hipFree(e->phase_dev); e->phase_dev = nullptr; }
-    free_days(e);
-    const size_t bytes = n_rows * e->P.Wd * 4 + 256;  // (tail pad: drec_levels reads whole 16-byte quads past a short level array)
-    // market track: resident (one entry per event) up to track_ring events per book, a ring of that many beyond
-    e->chunked = n_events > e->sw.track_ring;
-    e->S.track_len = e->chunked ? e->sw.track_ring : n_events;
-    e->S.track_mask = e->chunked ? e->sw.track_ring - 1 : 0x7fffffff;
-    const size_t track_bytes = (size_t)e->B * e->S.track_len * sizeof(Track);
-    // (a stream of the size of the one before it -- a fresh day per episode -- moves into the buffers that are there: freeing and
-    // allocating 31 + 18 GB cost more than the copy of a whole stream, round 6)
-    hipError_t err = hipSuccess;
-    if (!e->records_dev || e->records_bytes != bytes) {
-        if (e->records_dev) { hipFree(e->records_dev); e->records_dev = nullptr; }
-        err = hipMalloc((void**)&e->records_dev, bytes);
-        if (err != hipSuccess) { e->records_dev = nullptr; e->records_bytes = 0; lob_set_error("hipMalloc(records) failed"); return LOB_ENOMEM; }
-        e->records_bytes = bytes;
-    }
-    if (!e->track_dev || e->track_bytes != track_bytes) {
-        if (e->track_dev) { hipFree(e->track_dev); e->track_dev = nullptr; }
-        err = hipMalloc((void**)&e->track_dev, track_bytes);
-        if (err != hipSuccess) {
-            e->track_dev = nullptr; e->track_bytes = 0;
-            hipFree(e->records_dev);
-            e->records_dev = nullptr; e->records_bytes = 0;
-            lob_set_error("hipMalloc(track) failed");
-            return LOB_ENOMEM;
-        }
-        e->track_bytes = track_bytes;
-    }
-    e->S.track = e->track_dev;
-    e->S.records = e->records_dev;
-    e->S.n_events = n_events;
-    e->have_events = true;
-    e->was_reset = false;
-    return LOB_OK;
-}
-
-// A few host threads that copy one piece into a pinned staging buffer together, started once per upload (round 5 started and joined
-// up to seven per 64 MB piece: ~2 900 thread creations for 26.6 GB).  std::thread's constructor throws when the process may not
-// start another thread; the pool then runs with the workers it got -- none at all is fine, the caller's thread copies alone.
-struct CopyPool {
-    std::vector<std::thread> th;
-    std::mutex mu;
-    std::condition_variable cv_go, cv_done;
-    char* dst = nullptr;
-    const char* src = nullptr;
-    size_t nb = 0;
-    unsigned long long gen = 0;
-    unsigned pending = 0;
-    bool quit = false;
-    unsigned parts() const { return (unsigned)th.size() + 1; }
-    explicit CopyPool(unsigned want) {
-        try {
-            for (unsigned t = 1; t < want; t++) th.emplace_back([this, t] { worker(t); });
-        } catch (const std::system_error&) {
-        }
-    }
-    void worker(unsigned t) {
-        unsigned long long seen = 0;
-        for (;;) {
-            std::unique_lock<std::mutex> lk(mu);
-            cv_go.wait(lk, [&] { return quit || gen != seen; });
-            if (quit) return;
-            seen = gen;
-            char* d = dst; const char* s = src; const size_t n = nb; const unsigned np = parts();
-            lk.unlock();
-            if (t < np) { const size_t a = n * t / np, b = n * (t + 1) / np; memcpy(d + a, s + a, b - a); }
-            lk.lock();
-            if (--pending == 0) cv_done.notify_one();
-        }
-    }
-    void copy(char* d, const char* s, size_t n) {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            dst = d; src = s; nb = n; pending = (unsigned)th.size(); gen++;
-        }
-        cv_go.notify_all();
-        memcpy(d, s, n / parts());
-        std::unique_lock<std::mutex> lk(mu);
-        cv_done.wait(lk, [&] { return pending == 0; });
-    }
-    ~CopyPool() {
-        { std::lock_guard<std::mutex> lk(mu); quit = true; }
-        cv_go.notify_all();
-        for (auto& t : th) t.join();
-    }
-};
-
-// host ABI records -> HBM in the device layout.  Small uploads: one pageable copy into a temporary device buffer, one repack.
-// Big ones (the 26.6 GB of 65 536 private streams): 64 MB pieces through two pinned staging buffers -- a few host threads copy
-// piece k + 1 into its buffer while the DMA engine and the repack kernel are on piece k -- so the hand-over runs at what the
-// slower of the host's memcpy and the link gives instead of the runtime's pageable path, and the temporary device copy is two
-// pieces, not another whole stream.  Without pinned memory (a locked-memory limit; LOB_UPLOAD_PINNED=0 forces it, for the tests)
-// the same pieces go from the caller's pageable memory directly: slower, and still two pieces of device memory, never a second
-// whole stream.
-static int upload_records(lob_engine* e, const uint32_t* host_records, size_t n_records, hipStream_t st = nullptr, uint32_t* dst = nullptr) {
-    if (!st) st = e->stream;
-    if (!dst) dst = e->records_dev;
-    const size_t rec_bytes = (size_t)e->P.W * 4;
-    const size_t bytes = n_records * rec_bytes;
-    size_t piece_recs = std::max<size_t>(1, ((size_t)64 << 20) / rec_bytes);
-    if (e->sw.upload_piece_recs) piece_recs = (size_t)e->sw.upload_piece_recs;  // (tests: many small pieces)
-    if (n_records <= 2 * piece_recs) {
-        uint32_t* tmp = nullptr;
-        if (hipMalloc((void**)&tmp, bytes) != hipSuccess) { lob_set_error("hipMalloc(upload buffer) failed"); return LOB_ENOMEM; }
-        hipError_t err = hipMemcpyAsync(tmp, host_records, bytes, hipMemcpyHostToDevice, st);
-        if (err == hipSuccess) {
-            lobk_repack(st, (const uint32_t*)tmp, e->P.D, e->P.T, n_records, dst);
-            err = hipGetLastError();
-        }
-        if (err == hipSuccess) err = hipStreamSynchronize(st);
-        hipFree(tmp);
-        if (err != hipSuccess) { lob_set_error(std::string("record upload: ") + hipGetErrorString(err)); return LOB_EHIP; }
-        return LOB_OK;
-    }
-    const size_t piece_bytes = piece_recs * rec_bytes;
-    void* pinned[2] = {nullptr, nullptr};
-    uint32_t* tmp[2] = {nullptr, nullptr};
-    hipEvent_t done[2] = {nullptr, nullptr};
-    auto release = [&]() {
-        for (int i = 0; i < 2; i++) {
-            if (done[i]) hipEventDestroy(done[i]);
-            if (tmp[i]) hipFree(tmp[i]);
-            if (pinned[i]) hipHostFree(pinned[i]);
-        }
-    };
-    hipError_t err = hipSuccess;
-    for (int i = 0; i < 2 && err == hipSuccess; i++) {
-        err = hipMalloc((void**)&tmp[i], piece_bytes);
-        if (err == hipSuccess) err = hipEventCreateWithFlags(&done[i], hipEventDisableTiming);
-    }
-    if (err != hipSuccess) { release(); lob_set_error("hipMalloc(upload pieces) failed"); return LOB_ENOMEM; }
-    bool use_pinned = e->sw.upload_pinned;
-    for (int i = 0; i < 2 && use_pinned; i++)
-        if (hipHostMalloc(&pinned[i], piece_bytes, hipHostMallocDefault) != hipSuccess) {   // (no pinned memory to be had: the pageable pieces below)
-            (void)hipGetLastError();
-            pinned[i] = nullptr;
-            use_pinned = false;
-        }
-    if (!use_pinned) for (int i = 0; i < 2; i++) if (pinned[i]) { hipHostFree(pinned[i]); pinned[i] = nullptr; }
-    unsigned nt = std::thread::hardware_concurrency();
-    nt = nt < 1 ? 1 : nt > 8 ? 8 : nt;
-    int rc = LOB_OK;
-    try {
-        CopyPool pool(use_pinned ? nt : 1);
-        const size_t n_pieces = (n_records + piece_recs - 1) / piece_recs;
-        for (size_t k = 0; k < n_pieces && err == hipSuccess; k++) {
-            const int i = (int)(k & 1);
-            const size_t r0 = k * piece_recs, nr = std::min(piece_recs, n_records - r0), nb = nr * rec_bytes;
-            if (k >= 2) err = hipEventSynchronize(done[i]);  // (piece k - 2 has left this staging buffer and its device copy)
-            if (err != hipSuccess) break;
-            const char* src = reinterpret_cast<const char*>(host_records) + r0 * rec_bytes;
-            if (use_pinned) {
-                pool.copy(reinterpret_cast<char*>(pinned[i]), src, nb);
-                err = hipMemcpyAsync(tmp[i], pinned[i], nb, hipMemcpyHostToDevice, st);
-            } else {
-                err = hipMemcpyAsync(tmp[i], src, nb, hipMemcpyHostToDevice, st);   // (pageable: the runtime stages it, synchronously)
-            }
-            if (err == hipSuccess) {
-                lobk_repack(st, (const uint32_t*)tmp[i], e->P.D, e->P.T, nr, dst + r0 * (size_t)e->P.Wd);
-                err = hipGetLastError();
-            }
-            if (err == hipSuccess) err = hipEventRecord(done[i], st);
-        }
-    } catch (const std::exception& ex) {   // (nothing may cross the C ABI)
-        lob_set_error(std::string("record upload: ") + ex.what());
-        rc = LOB_ENOMEM;
-    }
-    const hipError_t err2 = hipStreamSynchronize(st);
-    if (err == hipSuccess) err = err2;
-    release();
-    if (rc != LOB_OK) return rc;
-    if (err != hipSuccess) { lob_set_error(std::string("record upload: ") + hipGetErrorString(err)); return LOB_EHIP; }
-    return LOB_OK;
-}
-
-int lob_load_events(lob_engine* e, const uint32_t* host_records, int32_t n_events) {
-    if (!e || !host_records || n_events < 2) { lob_set_error("lob_load_events: bad argument"); return LOB_EINVAL; }
-    HIPCHK(hipSetDevice(e->device));
-    int rc = lob_validate_stream(host_records, e->P.D, e->P.T, e->B, n_events);
-    if (rc != LOB_OK) return rc;
-    rc = set_records(e, n_events, (size_t)e->B * n_events);
-    if (rc != LOB_OK) return rc;
-    e->have_events = false;  // (a failed upload leaves no stream behind)
-    rc = upload_records(e, host_records, (size_t)e->B * n_events);
-    e->have_events = rc == LOB_OK;
-    return rc;
-}
-
-static int stage_join(lob_engine* e) {
-    if (e->stage_thread.joinable()) e->stage_thread.join();
-    if (e->stage_rc != LOB_OK) lob_set_error(e->stage_err);
-    return e->stage_rc;
-}
-int lob_stage_events(lob_engine* e, const uint32_t* host_records, int32_t n_events) {
-    if (!e || !host_records) { lob_set_error("lob_stage_events: bad argument"); return LOB_EINVAL; }
-    if (!e->have_events || e->lib || e->S.rec_phase || n_events != e->S.n_events) {
-        lob_set_error("lob_stage_events: needs a loaded per-book stream of the same length (lob_load_events first)");
-        return LOB_ESTATE;
-    }
-    if (e->stage_active) { lob_set_error("lob_stage_events: the stream staged before has not been adopted (lob_reset) or waited for"); return LOB_ESTATE; }
-    HIPCHK(hipSetDevice(e->device));
-    const size_t n_rows = (size_t)e->B * n_events;
-    if (!e->records_next) {
-        if (hipMalloc((void**)&e->records_next, n_rows * e->P.Wd * 4 + 256) != hipSuccess) { e->records_next = nullptr; lob_set_error("hipMalloc(second record buffer) failed"); return LOB_ENOMEM; }
-    }
-    if (!e->stream_up) HIPCHK(hipStreamCreateWithFlags(&e->stream_up, hipStreamNonBlocking));
-    e->stage_rc = LOB_OK;
-    e->stage_err.clear();
-    e->stage_active = true;
-    try {
-        e->stage_thread = std::thread([e, host_records, n_events, n_rows] {
-            int rc = hipSetDevice(e->device) == hipSuccess ? LOB_OK : LOB_EHIP;
-            if (rc == LOB_OK) rc = lob_validate_stream(host_records, e->P.D, e->P.T, e->B, n_events);
-            if (rc == LOB_OK) rc = upload_records(e, host_records, n_rows, e->stream_up, e->records_next);
-            e->stage_rc = rc;
-            if (rc != LOB_OK) e->stage_err = lob_last_error();   // (the error text is the failing thread's: handed to whoever waits)
-        });
-    } catch (const std::system_error&) {   // no thread to be had: the hand-over happens here and now
-        int rc = lob_validate_stream(host_records, e->P.D, e->P.T, e->B, n_events);
-        if (rc == LOB_OK) rc = upload_records(e, host_records, n_rows, e->stream_up, e->records_next);
-        e->stage_rc = rc;
-        if (rc != LOB_OK) e->stage_err = lob_last_error();
-    }
-    return LOB_OK;
-}
-int lob_stage_wait(lob_engine* e) {
-    if (!e) return LOB_EINVAL;
-    if (!e->stage_active) { lob_set_error("lob_stage_wait: nothing staged"); return LOB_ESTATE; }
-    return stage_join(e);
-}
-// (lob_reset) the staged stream becomes the current one: the buffers change places
-static int stage_adopt(lob_engine* e) {
-    if (!e->stage_active) return LOB_OK;
-    const int rc = stage_join(e);
-    e->stage_active = false;
-    if (rc != LOB_OK) return rc;
-    std::swap(e->records_dev, e->records_next);
-    e->S.records = e->records_dev;
-    return LOB_OK;
-}
-
-int lob_load_events_shared(lob_engine* e, const uint32_t* host_records, int64_t n_total, const int64_t* phase, int32_t n_events) {
-    if (!e || !host_records || !phase || n_events < 2 || n_total < n_events || n_total > INT32_MAX) {
-        lob_set_error("lob_load_events_shared: bad argument");
-        return LOB_EINVAL;
-    }
-    for (int b = 0; b < e->B; b++)
-        if (phase[b] < 0 || phase[b] + n_events > n_total) {
-            lob_set_error("lob_load_events_shared: phase[" + std::to_string(b) + "] + n_events runs past the stream");
-            return LOB_EINVAL;
-        }
-    HIPCHK(hipSetDevice(e->device));
-    int rc = lob_validate_stream(host_records, e->P.D, e->P.T, 1, (int32_t)n_total);
-    if (rc != LOB_OK) return rc;
-    rc = set_records(e, n_events, (size_t)n_total);
-    if (rc != LOB_OK) return rc;
-    // until the phases are in place the buffer (n_total rows) must not pass for a per-book stream (B * n_events rows)
-    e->have_events = false;
-    hipError_t err = hipMalloc((void**)&e->phase_dev, (size_t)e->B * sizeof(i64));
-    if (err != hipSuccess) { e->phase_dev = nullptr; lob_set_error("hipMalloc(phase) failed"); return LOB_ENOMEM; }
-    rc = upload_records(e, host_records, (size_t)n_total);
-    if (rc != LOB_OK) return rc;
-    HIPCHK(hipMemcpyAsync(e->phase_dev, phase, (size_t)e->B * sizeof(i64), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    e->have_events = true;
-    e->S.rec_phase = e->phase_dev;
-    return LOB_OK;
-}
-
-int lob_load_days(lob_engine* e, const uint32_t* host_records, const int64_t* day_first, int32_t n_days) {
-    if (!e || !host_records || !day_first || n_days < 1) { lob_set_error("lob_load_days: bad argument"); return LOB_EINVAL; }
-    if (day_first[0] != 0) { lob_set_error("lob_load_days: day_first[0] must be 0"); return LOB_EINVAL; }
-    int32_t longest = 0;
-    std::vector<i32> len((size_t)n_days);
-    for (int d = 0; d < n_days; d++) {
-        const int64_t n = day_first[d + 1] - day_first[d];
-        if (n < 2 || day_first[d + 1] > INT32_MAX) {
-            lob_set_error("lob_load_days: day " + std::to_string(d) + " has fewer than 2 events, or day_first is not monotone / runs past 2^31 records");
-            return LOB_EINVAL;
-        }
-        len[d] = (i32)n;
-        longest = std::max(longest, (int32_t)n);
-    }
-    const int64_t n_total = day_first[n_days];
-    HIPCHK(hipSetDevice(e->device));
-    for (int d = 0; d < n_days; d++) {
-        const int rc = lob_validate_stream(host_records + (size_t)day_first[d] * e->P.W, e->P.D, e->P.T, 1, len[d]);
-        if (rc != LOB_OK) return rc;
-    }
-    // the track is sized by the longest day: a ring when that one is longer than the resident track
-    int rc = set_records(e, longest, (size_t)n_total);
-    if (rc != LOB_OK) return rc;
-    e->have_events = false;   // (until the library and its tables are in place)
-    rc = upload_records(e, host_records, (size_t)n_total);
-    if (rc != LOB_OK) return rc;
-    const size_t B = (size_t)e->B;
-    bool ok = hipMalloc((void**)&e->day_first_dev, (size_t)n_days * sizeof(i64)) == hipSuccess &&
-              hipMalloc((void**)&e->day_len_dev, (size_t)n_days * sizeof(i32)) == hipSuccess &&
-              hipMalloc((void**)&e->day_rng, B * sizeof(uint32_t)) == hipSuccess && hipMalloc((void**)&e->day_explicit, B * sizeof(i32)) == hipSuccess &&
-              hipHostMalloc((void**)&e->day_explicit_host, B * sizeof(i32), hipHostMallocDefault) == hipSuccess &&
-              hipEventCreateWithFlags(&e->day_copied, hipEventDisableTiming) == hipSuccess;
-    for (int i = 0; i < 2 && ok; i++)
-        ok = hipMalloc((void**)&e->lib_phase[i], B * sizeof(i64)) == hipSuccess && hipMalloc((void**)&e->lib_len[i], B * sizeof(i32)) == hipSuccess &&
-             hipMalloc((void**)&e->lib_day[i], B * sizeof(i32)) == hipSuccess;
-    if (!ok) { (void)hipGetLastError(); free_days(e); lob_set_error("hipMalloc(day library tables) failed"); return LOB_ENOMEM; }
-    // RandomSampler's std::default_random_engine rng(seed) (sampler.h:34-39): minstd_rand0 seeded with (unsigned)(seed + global book id)
-    std::vector<uint32_t> rng(B);
-    for (size_t b = 0; b < B; b++) {
-        const uint32_t s = (uint32_t)(e->P.seed + e->P.book_id_offset + (u64)b);
-        rng[b] = s % 2147483647u == 0 ? 1u : s % 2147483647u;
-    }
-    HIPCHK(hipMemcpyAsync(e->day_first_dev, day_first, (size_t)n_days * sizeof(i64), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->day_len_dev, len.data(), (size_t)n_days * sizeof(i32), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->day_rng, rng.data(), B * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    e->lib = true;
-    e->lib_days = n_days;
-    e->have_events = true;
-    return LOB_OK;
-}
-
-// a selection may be made with a library loaded and no learner step half done
-static int days_ready(lob_engine* e, const char* who) {
-    if (!e->lib) { lob_set_error(std::string(who) + ": no day library loaded (lob_load_days)"); return LOB_ESTATE; }
-    if (e->half_open) { lob_set_error(std::string(who) + ": a learner step is half done (lob_td_step_begin without lob_td_step_end)"); return LOB_ESTATE; }
-    return LOB_OK;
-}
-// a selection for the next episode: days_draw_kernel writes the set the current episode does not play
-static int days_draw(lob_engine* e, int mode, int first, int n) {
-    HIPCHK(hipSetDevice(e->device));
-    const int nx = e->lib_cur < 0 ? 0 : e->lib_cur ^ 1;
-    TimedLaunch t(e, "days_draw_kernel", nullptr, true);
-    lobk_days_draw(e->stream, e->B, e->P.book_id_offset, mode, first, n, e->day_explicit, e->day_rng, e->day_first_dev, e->day_len_dev, e->lib_phase[nx],
-                   e->lib_len[nx], e->lib_day[nx]);
-    HIPCHK(hipGetLastError());
-    e->lib_pending = true;
-    return LOB_OK;
-}
-int lob_days_select(lob_engine* e, int32_t mode, int32_t first_day, int32_t n_days) {
-    if (!e) return LOB_EINVAL;
-    { int rc = days_ready(e, "lob_days_select"); if (rc) return rc; }
-    if ((mode != LOB_DAYS_RANDOM && mode != LOB_DAYS_IN_ORDER) || first_day < 0 || n_days < 1 || (int64_t)first_day + n_days > e->lib_days) {
-        lob_set_error("lob_days_select: bad mode, or days " + std::to_string(first_day) + " + " + std::to_string(n_days) + " outside the library");
-        return LOB_EINVAL;
-    }
-    return days_draw(e, mode, first_day, n_days);
-}
-int lob_days_set(lob_engine* e, const int32_t* host_day) {
-    if (!e || !host_day) { lob_set_error("lob_days_set: bad argument"); return LOB_EINVAL; }
-    { int rc = days_ready(e, "lob_days_set"); if (rc) return rc; }
-    for (int b = 0; b < e->B; b++)
-        if (host_day[b] < 0 || host_day[b] >= e->lib_days) { lob_set_error("lob_days_set: day of book " + std::to_string(b) + " outside the library"); return LOB_EINVAL; }
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipEventSynchronize(e->day_copied));   // (the copy of the selection before has left the pinned buffer)
-    memcpy(e->day_explicit_host, host_day, (size_t)e->B * sizeof(i32));
-    HIPCHK(hipMemcpyAsync(e->day_explicit, e->day_explicit_host, (size_t)e->B * sizeof(i32), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipEventRecord(e->day_copied, e->stream));
-    return days_draw(e, LOB_DAYS_EXPLICIT, 0, 1);
-}
-int lob_get_days(lob_engine* e, int32_t* host_out) {
-    if (!e || !host_out) { lob_set_error("lob_get_days: bad argument"); return LOB_EINVAL; }
-    if (!e->lib || e->lib_cur < 0) { lob_set_error("lob_get_days: no episode on a day library yet (lob_load_days, a selection, lob_reset)"); return LOB_ESTATE; }
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipMemcpyAsync(host_out, e->lib_day[e->lib_cur], (size_t)e->B * sizeof(i32), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return LOB_OK;
-}
-
-int lob_gen_events_device(lob_engine* e, const lob_gen_params* g) {
-    if (!e || !g || g->n_events < 2) { lob_set_error("lob_gen_events_device: bad argument"); return LOB_EINVAL; }
-    HIPCHK(hipSetDevice(e->device));
-    int rc = set_records(e, g->n_events, (size_t)e->B * g->n_events);
-    if (rc != LOB_OK) return rc;
-    lobk_gen_events(e->stream, *g, e->P.D, e->P.T, e->P.book_id_offset, e->B, e->records_dev);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return LOB_OK;
-}
-
-// env_kernel with EnginePlan::env_lanes books per wave
-static void launch_env(lob_engine* e, hipStream_t st, const i32* actions, int count_updates, int b0, int nb, int par) {
-    lobk_env(st, e->plan.env_lanes, e->P.T <= 2, (const DevParams*)e->P_dev, e->S, actions, count_updates, b0, nb, e->step_id, par);
-}
-// Long streams: let the pre-pass run on every `track_refill` steps (lob_kernels.h prepass_extend_kernel)
-static void maybe_refill_track(lob_engine* e) {
-    if (!e->chunked || ++e->steps_since_fill < e->sw.track_refill) return;
-    e->steps_since_fill = 0;
-    TimedLaunch t(e, "prepass_extend_kernel", nullptr, true);
-    lobk_prepass_extend(e->stream, e->P.T <= 2, e->sw.prepass_roles, (const DevParams*)e->P_dev, e->S);
-}
-// S0 of every group-0 triple on this step's list (lob_kernels.h memo_kernel): `which` 0 = for learn_kernel
-// (theta_t), 1 = for the next act_kernel (after the update)
-static void launch_memo(lob_engine* e, int par, int which, int reset_lpar = -1) {
-    TimedLaunch t(e, "memo_kernel");
-    hipLaunchKernelGGL(memo_kernel, dim3(256), dim3(256), 0, e->stream, e->P, e->S, (const uint32_t*)e->rnd_dev, par, which, (u64)e->theta_ver, reset_lpar);
-}
 int lob_reset(lob_engine* e) {
     if (!e) return LOB_EINVAL;
     if (!e->have_events) { lob_set_error("lob_reset: no event stream loaded"); return LOB_ESTATE; }
@@ -1364,586 +723,6 @@ int lob_reset(lob_engine* e) {
     return check_device_errors(e);
 }
 
-static int need_reset(lob_engine* e, const char* who) {
-    if (!e) return LOB_EINVAL;
-    if (!e->was_reset) { lob_set_error(std::string(who) + ": call lob_reset first"); return LOB_ESTATE; }
-    return LOB_OK;
-}
-// Between lob_td_step_begin and lob_td_step_end only the weight exchange may run (include/lob_engine.h): anything that moves
-// the books, the traces or the weights there would change what the second half consumes.
-// After a lob_snapshot_restore the learner's memory of the books' last transition (the rl::State objects, the traces, the hit lists)
-// belongs to another trajectory: the learner calls wait for the next lob_reset (include/lob_engine.h).
-static int not_restored(lob_engine* e, const char* who) {
-    if (e && e->restored) { lob_set_error(std::string(who) + ": books were put back by lob_snapshot_restore in this episode; the learner runs again after the next lob_reset"); return LOB_ESTATE; }
-    return LOB_OK;
-}
-static int not_mid_step(lob_engine* e, const char* who) {
-    if (e && e->half_open) { lob_set_error(std::string(who) + ": a learner step is half done (lob_td_step_begin without lob_td_step_end)"); return LOB_ESTATE; }
-    return LOB_OK;
-}
-
-// The step log's row of every selected book that has just completed a step (lob_tu_steplog.hip step_log_kernel): on the main stream
-// behind the step's last kernel; not launched while the log is off or waits for its first lob_reset.
-static void launch_step_log(lob_engine* e) {
-    if (!e->slog_armed) return;
-    TimedLaunch t(e, "step_log_kernel");
-    StepLogSrc s;
-    s.done = e->S.done; s.time_ms = e->S.time_ms; s.rec_cur = e->S.rec_cur; s.last_action = e->S.last_action;
-    s.ask_level = e->S.ask_level; s.bid_level = e->S.bid_level; s.total_ticks = e->S.total_ticks;
-    s.position = e->S.position;
-    s.ask_quote = e->S.ask_quote; s.bid_quote = e->S.bid_quote; s.pnl_step = e->S.pnl_step;
-    s.ep_pnl = e->S.ep_pnl; s.ep_bandh = e->S.ep_bandh; s.ep_reward = e->S.ep_reward;
-    s.records = e->S.records; s.rec_phase = e->S.rec_phase;
-    s.n_events = e->S.n_events; s.Wd = e->P.Wd; s.w_ask0 = drec_ask_px(e->P.D, e->P.T); s.w_bid0 = drec_bid_px(e->P.D, e->P.T);
-    s.sel = e->slog_sel; s.n_sel = e->slog_n; s.cap = e->slog_cap;
-    s.rows = e->slog_rows; s.n_rows = e->slog_cnt; s.n_lost = e->slog_cnt + e->slog_n;
-    lobk_step_log(e->stream, s);
-}
-
-int lob_step(lob_engine* e, const int32_t* host_actions) {
-    int rc = need_reset(e, "lob_step");
-    if (rc) return rc;
-    if ((rc = not_mid_step(e, "lob_step"))) return rc;
-    if (!host_actions) { lob_set_error("lob_step: actions == NULL"); return LOB_EINVAL; }
-    for (int b = 0; b < e->B; b++)
-        if (host_actions[b] < 0 || host_actions[b] >= LOB_N_ACTIONS) { lob_set_error("lob_step: action out of range"); return LOB_EINVAL; }
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipMemcpyAsync(e->actions_dev, host_actions, (size_t)e->B * 4, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemsetAsync(e->S.mk_count, 0, 2 * sizeof(i32), e->stream));  // claims of this step go on a fresh list (nobody evaluates it)
-    e->step_id++;
-    e->hits_ok = false;
-    {
-        TimedLaunch t(e, "env_kernel");
-        launch_env(e, e->stream, (const i32*)e->actions_dev, 0, 0, e->B, 0);
-    }
-    launch_step_log(e);
-    maybe_refill_track(e);
-    HIPCHK(hipGetLastError());
-    return check_device_errors(e);
-}
-
-// ---- vector-env interface (include/lob_engine.h lob_vec_*; lob_tu_vec.hip) ----
-static VecSrc vec_src(lob_engine* e) {
-    VecSrc s;
-    s.hdr = e->S.hdr; s.done = e->S.done; s.time_ms = e->S.time_ms; s.vars = e->S.vars;
-    s.open_ms = e->P.open_ms; s.close_ms = e->P.close_ms; s.B = e->B; s.V = e->P.V;
-    s.n_bad = e->vec_bad;
-    return s;
-}
-static int vec_entry(lob_engine* e, const lob_vec_out* out, const char* who) {
-    if (!e || !out) { lob_set_error(std::string(who) + ": NULL argument"); return LOB_EINVAL; }
-    int rc = need_reset(e, who);
-    if (rc) return rc;
-    return not_mid_step(e, who);
-}
-
-// lob_step with the actions read, checked and armed on the device and the observation written there: four launches (five with the
-// step log on) and two small memsets on the engine's stream, and the call returns.
-int lob_vec_step(lob_engine* e, const int32_t* dev_actions, const lob_vec_out* out) {
-    if (!dev_actions) { lob_set_error("lob_vec_step: NULL argument"); return LOB_EINVAL; }
-    int rc = vec_entry(e, out, "lob_vec_step");
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipMemsetAsync(e->S.mk_count, 0, 2 * sizeof(i32), e->stream));  // claims of this step go on a fresh list (nobody evaluates it)
-    if (out->n_live) HIPCHK(hipMemsetAsync(out->n_live, 0, sizeof(i32), e->stream));
-    e->step_id++;
-    e->hits_ok = false;
-    const VecSrc s = vec_src(e);
-    {
-        TimedLaunch t(e, "vec_actions_kernel");
-        lobk_vec_actions(e->stream, s, dev_actions);
-    }
-    {
-        TimedLaunch t(e, "env_kernel");
-        launch_env(e, e->stream, (const i32*)nullptr, 0, 0, e->B, 0);   // (no action array: go = h.stepped != 0, as armed above)
-    }
-    launch_step_log(e);
-    {
-        TimedLaunch t(e, "vec_observe_kernel");
-        lobk_vec_observe(e->stream, false, true, s, (const DevParams*)e->P_dev, e->S, *out);
-    }
-    maybe_refill_track(e);
-    HIPCHK(hipGetLastError());
-    return LOB_OK;
-}
-
-int lob_vec_observe(lob_engine* e, const lob_vec_out* out) {
-    int rc = vec_entry(e, out, "lob_vec_observe");
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(e->device));
-    if (out->n_live) HIPCHK(hipMemsetAsync(out->n_live, 0, sizeof(i32), e->stream));
-    {
-        TimedLaunch t(e, "vec_observe_derive_kernel", nullptr, true);
-        lobk_vec_observe(e->stream, true, false, vec_src(e), (const DevParams*)e->P_dev, e->S, *out);
-    }
-    HIPCHK(hipGetLastError());
-    return LOB_OK;
-}
-
-int lob_vec_status(lob_engine* e, int64_t* n_bad_actions) {
-    if (!e) { lob_set_error("lob_vec_status: NULL engine"); return LOB_EINVAL; }
-    HIPCHK(hipSetDevice(e->device));
-    i32 flag = 0;
-    u64 bad = 0;
-    HIPCHK(hipMemcpyAsync(&flag, e->S.error_flag, sizeof flag, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(&bad, e->vec_bad, sizeof bad, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemsetAsync(e->vec_bad, 0, sizeof(u64), e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (n_bad_actions) *n_bad_actions = (int64_t)bad;
-    if (flag) return device_error_rc(flag);
-    if (bad) { lob_set_error("lob_vec_step: " + std::to_string(bad) + " action(s) out of range since the last lob_vec_status; those books were not stepped"); return LOB_EINVAL; }
-    return LOB_OK;
-}
-
-// The order book and the agent's own words of every book into the caller's device buffers (lob_tu_vecbook.hip vec_book_kernel): one
-// launch on the engine's stream, nothing read back, nothing changed.
-int lob_vec_book(lob_engine* e, const lob_vec_book_out* out) {
-    if (!e || !out) { lob_set_error("lob_vec_book: NULL argument"); return LOB_EINVAL; }
-    int rc = need_reset(e, "lob_vec_book");
-    if (rc) return rc;
-    if ((rc = not_mid_step(e, "lob_vec_book"))) return rc;
-    if (!out->levels && !out->own && !out->time_ms) return LOB_OK;
-    HIPCHK(hipSetDevice(e->device));
-    VecBookSrc s;
-    s.records = e->S.records; s.rec_phase = e->S.rec_phase; s.rec_cur = e->S.rec_cur;
-    s.n_events = e->S.n_events; s.Wd = e->P.Wd; s.D = e->P.D;
-    s.w_ask_px = drec_ask_px(e->P.D, e->P.T); s.w_ask_vol = drec_ask_vol(e->P.D, e->P.T);
-    s.w_bid_px = drec_bid_px(e->P.D, e->P.T); s.w_bid_vol = drec_bid_vol(e->P.D, e->P.T);
-    s.position = e->S.position;
-    s.a_osz = e->S.a_osz; s.a_oex = e->S.a_oex; s.a_oqh = e->S.a_oqh; s.b_osz = e->S.b_osz; s.b_oex = e->S.b_oex; s.b_oqh = e->S.b_oqh;
-    s.a_on = e->S.a_on; s.b_on = e->S.b_on; s.last_action = e->S.last_action; s.total_ticks = e->S.total_ticks; s.time_ms = e->S.time_ms;
-    s.a_opx = e->S.a_opx; s.b_opx = e->S.b_opx; s.ask_quote = e->S.ask_quote; s.bid_quote = e->S.bid_quote;
-    s.pnl_step = e->S.pnl_step; s.ep_pnl = e->S.ep_pnl; s.ep_reward = e->S.ep_reward;
-    s.B = e->B;
-    {
-        TimedLaunch t(e, "vec_book_kernel", nullptr, true);
-        lobk_vec_book(e->stream, s, *out);
-    }
-    HIPCHK(hipGetLastError());
-    return LOB_OK;
-}
-
-// The last K event records of every book into the caller's device buffers (lob_tu_vechist.hip vec_hist_kernel): one launch on the
-// engine's stream, nothing read back, nothing changed.  e->S.records as it is now: a stream handed over by lob_stage_events is followed.
-int lob_vec_history(lob_engine* e, int32_t K, const lob_vec_hist_out* out) {
-    if (!e || !out) { lob_set_error("lob_vec_history: NULL argument"); return LOB_EINVAL; }
-    if (K < 1 || K > LOB_MAX_HISTORY) { lob_set_error("lob_vec_history: K = " + std::to_string(K) + " is outside [1, " + std::to_string(LOB_MAX_HISTORY) + "]"); return LOB_EINVAL; }
-    int rc = need_reset(e, "lob_vec_history");
-    if (rc) return rc;
-    if ((rc = not_mid_step(e, "lob_vec_history"))) return rc;
-    if (!out->levels && !out->trades && !out->time_ms && !out->n_valid && !out->rec) return LOB_OK;
-    HIPCHK(hipSetDevice(e->device));
-    VecHistSrc s;
-    s.records = e->S.records; s.rec_phase = e->S.rec_phase; s.rec_cur = e->S.rec_cur; s.rec_len = e->S.rec_len;
-    s.n_events = e->S.n_events; s.Wd = e->P.Wd; s.D = e->P.D; s.T = e->P.T; s.B = e->B;
-    s.w_ask_px = drec_ask_px(e->P.D, e->P.T); s.w_ask_vol = drec_ask_vol(e->P.D, e->P.T);
-    s.w_bid_px = drec_bid_px(e->P.D, e->P.T); s.w_bid_vol = drec_bid_vol(e->P.D, e->P.T); s.w_trades = drec_trades(e->P.D, e->P.T);
-    {
-        TimedLaunch t(e, "vec_hist_kernel", nullptr, true);
-        lobk_vec_history(e->stream, s, K, *out);
-    }
-    HIPCHK(hipGetLastError());
-    return LOB_OK;
-}
-
-// The engine's own Q values and policy actions for every book, into the caller's device buffers (lob_tu_vecact.hip vec_act_kernel;
-// DESIGN.md 7h): one launch on the engine's stream, nothing read back.  The kernel reads the state through its device-resident copy,
-// which the first lob_reset has uploaded (sync_state); every array it follows from there is allocated by lob_create and stays.
-// Not refused after lob_snapshot_restore: it reads the books' latest getState(), which the restore put back, and nothing of the
-// learner's memory of the last transition.
-int lob_vec_act(lob_engine* e, int32_t mode, const lob_vec_act_out* out) {
-    if (!e || !out) { lob_set_error("lob_vec_act: NULL argument"); return LOB_EINVAL; }
-    if (mode < LOB_ACT_GREEDY || mode > LOB_ACT_ARGMAX) { lob_set_error("lob_vec_act: mode " + std::to_string(mode) + " is none of LOB_ACT_GREEDY, LOB_ACT_BEHAVIOUR, LOB_ACT_ARGMAX"); return LOB_EINVAL; }
-    int rc = need_reset(e, "lob_vec_act");
-    if (rc) return rc;
-    if ((rc = not_mid_step(e, "lob_vec_act"))) return rc;
-    if (!out->action && !out->q) return LOB_OK;
-    HIPCHK(hipSetDevice(e->device));
-    VecActSrc a;
-    a.rows = nullptr; a.theta = nullptr; a.nz = nullptr;
-    a.n = e->B; a.mode = mode;
-    a.action = out->action; a.q = out->q;
-    {
-        TimedLaunch t(e, "vec_act_kernel", nullptr, true);
-        lobk_vec_act(e->stream, e->P.algo == LOB_ALGO_DOUBLE_Q, e->n_cus, LOB_PS(e), (const uint32_t*)e->rnd_dev, a);
-    }
-    HIPCHK(hipGetLastError());
-    return LOB_OK;
-}
-
-// What lob_vec_step would write under each action of the mask, into the caller's device buffers (lob_tu_vecpeek.hip vec_peek_kernel;
-// DESIGN.md 7j): one launch on the engine's stream, nothing read back, nothing of the engine's state changed -- no step number, no
-// memo list, no step-log row, no refill of the track.  Not refused after lob_snapshot_restore: it reads the environment only.
-// Refused on a ring track, like the snapshots: the look-ahead reads the entries ahead of the cursor exactly as the step does, but
-// that they are all there between two refills whenever it is called has not been shown.
-int lob_vec_peek(lob_engine* e, uint32_t action_mask, const lob_vec_peek_out* out) {
-    if (!e || !out) { lob_set_error("lob_vec_peek: NULL argument"); return LOB_EINVAL; }
-    if (action_mask == 0 || (action_mask & ~(uint32_t)LOB_PEEK_ALL)) {
-        lob_set_error("lob_vec_peek: action_mask " + std::to_string(action_mask) + " is empty or has a bit at or above LOB_N_ACTIONS"); return LOB_EINVAL;
-    }
-    int rc = need_reset(e, "lob_vec_peek");
-    if (rc) return rc;
-    if ((rc = not_mid_step(e, "lob_vec_peek"))) return rc;
-    if (e->chunked) { lob_set_error("lob_vec_peek: the market track of this stream is a ring (longer than LOB_TRACK_RING events)"); return LOB_ESTATE; }
-    if (!out->obs && !out->reward && !out->terminal && !out->stepped) return LOB_OK;
-    HIPCHK(hipSetDevice(e->device));
-    PeekSrc a;
-    a.B = e->B; a.Bpad = (e->B + 63) / 64 * 64;
-    a.n_act = 0;
-    for (int k = 0; k < 12; k++) a.act[k] = 0;
-    for (int k = 0; k < LOB_N_ACTIONS; k++)
-        if (action_mask >> k & 1u) a.act[a.n_act++] = (uint8_t)k;
-    a.out = *out;
-    {
-        TimedLaunch t(e, "vec_peek_kernel", nullptr, true);
-        lobk_vec_peek(e->stream, e->P.T <= 2, (const DevParams*)e->P_dev, e->S, a);
-    }
-    HIPCHK(hipGetLastError());
-    return LOB_OK;
-}
-
-// What `horizon` consecutive lob_vec_step calls would write under each of `n_plans` plans, into the caller's device buffers
-// (lob_tu_vecroll.hip vec_rollout_kernel): one launch on the engine's stream, nothing read back, nothing of the engine's
-// state changed.  Allowed and refused where lob_vec_peek is.  The one allocation: the workspace of the PnL windows' entries the plans
-// themselves push, needed when the reward reads the windows (LOB_REWARD_NORMED) and 1 < lb_pnl < horizon -- 2 * lb_pnl * n_plans *
-// Bpad doubles, made by the first call that needs it and grown (hipFree + hipMalloc: both synchronise the device) only by a call
-// that needs more than any before it.
-int lob_vec_rollout(lob_engine* e, const int32_t* dev_actions, int n_plans, int horizon, double gamma, const lob_vec_rollout_out* out) {
-    if (!e || !out || !dev_actions) { lob_set_error("lob_vec_rollout: NULL argument"); return LOB_EINVAL; }
-    if (n_plans < 1 || n_plans > LOB_MAX_ROLLOUT_PLANS) {
-        lob_set_error("lob_vec_rollout: n_plans = " + std::to_string(n_plans) + " is outside [1, " + std::to_string(LOB_MAX_ROLLOUT_PLANS) + "]"); return LOB_EINVAL;
-    }
-    if (horizon < 1 || horizon > LOB_MAX_ROLLOUT_STEPS) {
-        lob_set_error("lob_vec_rollout: horizon = " + std::to_string(horizon) + " is outside [1, " + std::to_string(LOB_MAX_ROLLOUT_STEPS) + "]"); return LOB_EINVAL;
-    }
-    if (!(gamma >= 0.0 && gamma <= 1.0)) { lob_set_error("lob_vec_rollout: gamma = " + std::to_string(gamma) + " is outside [0, 1]"); return LOB_EINVAL; }
-    int rc = need_reset(e, "lob_vec_rollout");
-    if (rc) return rc;
-    if ((rc = not_mid_step(e, "lob_vec_rollout"))) return rc;
-    if (e->chunked) { lob_set_error("lob_vec_rollout: the market track of this stream is a ring (longer than LOB_TRACK_RING events)"); return LOB_ESTATE; }
-    if (!out->obs && !out->reward && !out->terminal && !out->stepped && !out->ret) return LOB_OK;
-    HIPCHK(hipSetDevice(e->device));
-    RolloutSrc a;
-    a.actions = dev_actions;
-    a.B = e->B; a.Bpad = (e->B + 63) / 64 * 64;
-    a.n_plans = n_plans; a.horizon = horizon;
-    a.gamma = gamma;
-    a.shadow = nullptr;
-    a.out = *out;
-    const int w = e->S.pnl_ups.w;
-    if (e->P.reward_measure == LOB_REWARD_NORMED && w > 1 && w < horizon) {
-        const size_t need = 2 * (size_t)w * (size_t)n_plans * (size_t)a.Bpad;
-        if (need > e->roll_ws_elems) {
-            f64* ws = nullptr;
-            if (e->roll_ws) { hipFree(e->roll_ws); e->roll_ws = nullptr; e->roll_ws_elems = 0; }
-            if (hipMalloc((void**)&ws, need * sizeof(f64)) != hipSuccess) {
-                (void)hipGetLastError();
-                lob_set_error("lob_vec_rollout: no room for the PnL windows' workspace (" + std::to_string(need * sizeof(f64)) + " bytes; fewer plans or a shorter horizon per call)");
-                return LOB_ENOMEM;
-            }
-            e->roll_ws = ws; e->roll_ws_elems = need;
-        }
-        a.shadow = e->roll_ws;
-    }
-    {
-        TimedLaunch t(e, "vec_rollout_kernel", nullptr, true);
-        lobk_vec_rollout(e->stream, e->P.T <= 2, (const DevParams*)e->P_dev, e->S, a);
-    }
-    HIPCHK(hipGetLastError());
-    return LOB_OK;
-}
-
-// lob_q_values with both ends in device memory: the same kernel over the caller's rows, under theta (book 0's under private theta).
-int lob_vec_q(lob_engine* e, const float* dev_vars, int32_t n, double* dev_q) {
-    if (!e || !dev_vars || !dev_q || n < 1) { lob_set_error("lob_vec_q: bad argument"); return LOB_EINVAL; }
-    HIPCHK(hipSetDevice(e->device));
-    VecActSrc a;
-    a.rows = dev_vars; a.theta = (const f64*)e->S.theta; a.nz = (const uint32_t*)e->S.theta_nz;
-    a.n = n; a.mode = LOB_ACT_ARGMAX;
-    a.action = nullptr; a.q = dev_q;
-    {
-        TimedLaunch t(e, "vec_q_kernel", nullptr, true);
-        lobk_vec_act(e->stream, false, e->n_cus, LOB_PS(e), (const uint32_t*)e->rnd_dev, a);
-    }
-    HIPCHK(hipGetLastError());
-    return LOB_OK;
-}
-
-// ---- tile features and external weight updates (include/lob_engine.h lob_vec_features / lob_vec_update; lob_tu_vecfeat.hip) ----
-int lob_vec_terms(lob_engine* e, int32_t host_out[27]) {
-    if (!e || !host_out) { lob_set_error("lob_vec_terms: NULL argument"); return LOB_EINVAL; }
-    for (int i = 0; i < 27; i++) host_out[i] = (int32_t)e->vec_terms[i];   // (< M <= 2^31 - 1)
-    return LOB_OK;
-}
-// The argument checks the two device calls share: the rows' rule of lob_vec_act / lob_vec_q
-static int vec_feat_entry(lob_engine* e, const float* dev_vars, int32_t n, const char* who) {
-    if (!e) { lob_set_error(std::string(who) + ": NULL engine"); return LOB_EINVAL; }
-    if (n < 1) { lob_set_error(std::string(who) + ": n = " + std::to_string(n) + " (at least one row)"); return LOB_EINVAL; }
-    if (!dev_vars && n != e->B) { lob_set_error(std::string(who) + ": n = " + std::to_string(n) + " but dev_vars == NULL means the engine's " + std::to_string(e->B) + " books"); return LOB_EINVAL; }
-    int rc = not_mid_step(e, who);
-    if (rc) return rc;
-    return dev_vars ? LOB_OK : need_reset(e, who);
-}
-// The hash sums / tile indices of n states into the caller's device buffers: one launch on the engine's stream, nothing changed.
-int lob_vec_features(lob_engine* e, const float* dev_vars, int32_t n, const int32_t* dev_actions, const lob_vec_feat_out* out) {
-    if (e && !out) { lob_set_error("lob_vec_features: NULL out"); return LOB_EINVAL; }
-    if (e && out->idx && !dev_actions) { lob_set_error("lob_vec_features: idx wanted without dev_actions"); return LOB_EINVAL; }
-    int rc = vec_feat_entry(e, dev_vars, n, "lob_vec_features");
-    if (rc) return rc;
-    if (!out->sums && !out->idx) return LOB_OK;
-    HIPCHK(hipSetDevice(e->device));
-    VecFeatSrc a;
-    memset(&a, 0, sizeof a);
-    a.rows = dev_vars; a.actions = out->idx ? dev_actions : nullptr; a.n = n;
-    a.sums = out->sums; a.idx = out->idx;
-    {
-        TimedLaunch t(e, "vec_features_kernel", nullptr, true);
-        lobk_vec_feat(e->stream, e->n_cus, LOB_PS(e), (const uint32_t*)e->rnd_dev, a);
-    }
-    HIPCHK(hipGetLastError());
-    return LOB_OK;
-}
-// theta[tile] += step over the tiles of (row, action), from outside a step.  On the device the kernel keeps the maps as
-// delta_apply_kernel does; here the host does what lob_theta_set does around its kernels -- except for the multi-GPU base, which
-// stays: the update is a local change and the next exchange carries it.
-int lob_vec_update(lob_engine* e, const float* dev_vars, int32_t n, const int32_t* dev_actions, const double* dev_step, int32_t second) {
-    if (e && (!dev_actions || !dev_step)) { lob_set_error("lob_vec_update: NULL argument"); return LOB_EINVAL; }
-    if (e && second != 0 && second != 1) { lob_set_error("lob_vec_update: second = " + std::to_string(second) + " is neither 0 nor 1"); return LOB_EINVAL; }
-    if (e && second && e->P.algo != LOB_ALGO_DOUBLE_Q) { lob_set_error("lob_vec_update: second = 1 needs LOB_ALGO_DOUBLE_Q (there is no theta_b)"); return LOB_EINVAL; }
-    int rc = vec_feat_entry(e, dev_vars, n, "lob_vec_update");
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(e->device));
-    VecFeatSrc a;
-    memset(&a, 0, sizeof a);
-    a.rows = dev_vars; a.actions = dev_actions; a.n = n; a.step = dev_step;
-    a.theta = second ? e->S.theta_b : e->S.theta;
-    a.nz = second ? e->S.theta_b_nz : e->S.theta_nz;
-    if (e->P.memo) {   // (double Q: one set of maps for both vectors)
-        a.nzx = e->S.theta_nzx; a.nzc = e->S.theta_nzc; a.nzd = e->S.theta_nzd; a.nzm = e->S.theta_nzm; a.nzd_terms = e->S.nzd_terms;
-        a.cshift = e->P.cshift;
-    }
-    a.nz_epoch = e->S.nz_epoch;
-    a.tag = e->vec_upd_tag;
-    a.launch = e->vec_upd_launch = e->vec_upd_launch == INT32_MAX ? 1 : e->vec_upd_launch + 1;
-    a.n_bad = e->vec_bad;
-    e->theta_ver++;  // memo records computed under the old weights are void
-    e->hits_ok = false;
-    e->hint_step = 0;  // (... and so is what the learn kernels handed back under them)
-    e->rest_recent = 0;
-    {
-        TimedLaunch t(e, "vec_update_kernel", nullptr, true);
-        lobk_vec_feat(e->stream, e->n_cus, LOB_PS(e), (const uint32_t*)e->rnd_dev, a);
-    }
-    if (e->P.memo && e->was_reset) launch_memo(e, e->last_par, 1);  // the current triples under the new weights: the next act stays on the fast path
-    HIPCHK(hipGetLastError());
-    return LOB_OK;
-}
-
-// ---- book snapshots (include/lob_engine.h lob_snapshot_*; lob_tu_snapshot.hip) ----
-// The descriptor table of the arrays a snapshot holds and their places in a slot buffer, built once per engine with the first save:
-// every array of LOB_ENV_FIELDS, the rolling means pnl_ups / pnl_downs, then the per-book records (LHdr's five environment words,
-// slot 2 of vars).  Arrays at multiples of 16 bytes, in the live layout.
-static int snap_prepare(lob_engine* e) {
-    if (e->snap_tab) return LOB_OK;
-    const size_t B = (size_t)e->B;
-    std::vector<SnapRow> r4, r8;
-    std::vector<SnapArr> arrs;
-    size_t off = 0, max_bytes = 0;
-    auto add = [&](void* live, size_t width, size_t rows) {
-        const size_t bytes = rows * B * width;
-        arrs.push_back(SnapArr{live, (u64)off, (u64)bytes, 0});
-        for (size_t r = 0; r < rows; r++) (width == 4 ? r4 : r8).push_back(SnapRow{(char*)live + r * B * width, (u64)(off + r * B * width)});
-        max_bytes = std::max(max_bytes, bytes);
-        off = (off + bytes + 15) & ~(size_t)15;
-    };
-#define X(t, n) static_assert(sizeof(t) == 4 || sizeof(t) == 8, "two element widths"); add(e->S.n.p, sizeof(t), 1);
-    LOB_ENV_FIELDS(X)
-#undef X
-    for (const RMPtrs* m : {&e->S.pnl_ups, &e->S.pnl_downs}) {
-        add(m->ring.p, 8, (size_t)m->w); add(m->cnt.p, 4, 1); add(m->head.p, 4, 1); add(m->sum.p, 8, 1); add(m->mean.p, 8, 1); add(m->s.p, 8, 1);
-    }
-    SnapArgs& a = e->snap_args;
-    a.off_hdr = off; off = (off + 4 * B * 4 + 15) & ~(size_t)15;
-    a.off_reward = off; off = (off + B * 8 + 15) & ~(size_t)15;
-    a.off_vars = off; off += B * 64;
-    a.n4 = (i32)r4.size(); a.n8 = (i32)r8.size(); a.n_arr = (i32)arrs.size(); a.B = e->B;
-    a.max_bytes = max_bytes;
-    a.hdr = e->S.hdr.p; a.vars = e->S.vars.p;
-    r4.insert(r4.end(), r8.begin(), r8.end());
-    const size_t rows_bytes = r4.size() * sizeof(SnapRow), arrs_bytes = arrs.size() * sizeof(SnapArr);
-    void* tab = nullptr;
-    if (hipMalloc(&tab, rows_bytes + arrs_bytes) != hipSuccess) { (void)hipGetLastError(); lob_set_error("lob_snapshot_save: no room for the descriptor table"); return LOB_ENOMEM; }
-    if (hipMemcpy(tab, r4.data(), rows_bytes, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy((char*)tab + rows_bytes, arrs.data(), arrs_bytes, hipMemcpyHostToDevice) != hipSuccess) {
-        hipFree(tab);
-        lob_set_error("lob_snapshot_save: descriptor table upload failed");
-        return LOB_EHIP;
-    }
-    a.rows = (const SnapRow*)tab;
-    a.arrs = (const SnapArr*)((char*)tab + rows_bytes);
-    e->snap_tab = tab;
-    e->snap_bytes = off;
-    return LOB_OK;
-}
-static int snap_entry(lob_engine* e, int32_t slot, const char* who) {
-    if (!e) { lob_set_error(std::string(who) + ": NULL engine"); return LOB_EINVAL; }
-    if (slot < 0 || slot >= LOB_MAX_SNAPSHOTS) { lob_set_error(std::string(who) + ": slot " + std::to_string(slot) + " is outside [0, " + std::to_string(LOB_MAX_SNAPSHOTS) + ")"); return LOB_EINVAL; }
-    int rc = need_reset(e, who);
-    if (rc) return rc;
-    if ((rc = not_mid_step(e, who))) return rc;
-    if (e->chunked) { lob_set_error(std::string(who) + ": the market track of this stream is a ring (longer than LOB_TRACK_RING events): entries before the cursor are gone, no earlier state can be served"); return LOB_ESTATE; }
-    return LOB_OK;
-}
-int lob_snapshot_save(lob_engine* e, int32_t slot, const uint8_t* dev_mask) {
-    int rc = snap_entry(e, slot, "lob_snapshot_save");
-    if (rc) return rc;
-    if (dev_mask && !e->snap_valid[slot]) { lob_set_error("lob_snapshot_save: a masked save needs a slot that holds a full save (NULL mask) of this episode"); return LOB_ESTATE; }
-    HIPCHK(hipSetDevice(e->device));
-    if ((rc = snap_prepare(e))) return rc;
-    if (!e->snap_buf[slot]) {   // (the slot's one allocation: hipMalloc synchronises the device)
-        if (hipMalloc(&e->snap_buf[slot], e->snap_bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            e->snap_buf[slot] = nullptr;
-            lob_set_error("lob_snapshot_save: no room for the slot's buffer (" + std::to_string(e->snap_bytes) + " bytes)");
-            return LOB_ENOMEM;
-        }
-    }
-    {
-        TimedLaunch t(e, dev_mask ? "snapshot_masked_kernel" : "snapshot_all_kernel", nullptr, true);
-        lobk_snapshot(e->stream, false, e->snap_args, e->snap_buf[slot], dev_mask);
-    }
-    HIPCHK(hipGetLastError());
-    e->snap_valid[slot] = true;
-    return LOB_OK;
-}
-int lob_snapshot_restore(lob_engine* e, int32_t slot, const uint8_t* dev_mask) {
-    int rc = snap_entry(e, slot, "lob_snapshot_restore");
-    if (rc) return rc;
-    if (e->slog_n) { lob_set_error("lob_snapshot_restore: the step log is enabled (a row is due where total_ticks > n_rows + n_lost: total_ticks cannot go back under it)"); return LOB_ESTATE; }
-    if (!e->snap_valid[slot] || !e->snap_buf[slot]) { lob_set_error("lob_snapshot_restore: slot " + std::to_string(slot) + " holds no save of this episode"); return LOB_ESTATE; }
-    HIPCHK(hipSetDevice(e->device));
-    {
-        TimedLaunch t(e, dev_mask ? "snapshot_masked_kernel" : "snapshot_all_kernel", nullptr, true);
-        lobk_snapshot(e->stream, true, e->snap_args, e->snap_buf[slot], dev_mask);
-    }
-    HIPCHK(hipGetLastError());
-    e->restored = true;
-    e->hits_ok = false;
-    return LOB_OK;
-}
-int lob_snapshot_free(lob_engine* e, int32_t slot) {
-    if (!e) { lob_set_error("lob_snapshot_free: NULL engine"); return LOB_EINVAL; }
-    if (slot < 0 || slot >= LOB_MAX_SNAPSHOTS) { lob_set_error("lob_snapshot_free: slot " + std::to_string(slot) + " is outside [0, " + std::to_string(LOB_MAX_SNAPSHOTS) + ")"); return LOB_EINVAL; }
-    if (!e->snap_buf[slot]) return LOB_OK;
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipStreamSynchronize(e->stream));   // (a save or restore still queued uses the buffer)
-    hipFree(e->snap_buf[slot]);
-    e->snap_buf[slot] = nullptr;
-    e->snap_valid[slot] = false;
-    return LOB_OK;
-}
-
-int lob_get_state(lob_engine* e, float* host_out) {
-    int rc = need_reset(e, "lob_get_state");
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(e->device));
-    f32* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, (size_t)e->B * e->P.V * 4));
-    lobk_get_state(e->stream, (const DevParams*)e->P_dev, e->S, d, (f64*)nullptr);
-    hipError_t err = hipMemcpyAsync(host_out, d, (size_t)e->B * e->P.V * 4, hipMemcpyDeviceToHost, e->stream);
-    hipStreamSynchronize(e->stream);
-    hipFree(d);
-    HIPCHK(err);
-    return LOB_OK;
-}
-
-int lob_get_reward(lob_engine* e, double* host_out) {
-    int rc = need_reset(e, "lob_get_reward");
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(e->device));
-    f64* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, (size_t)e->B * 8));
-    lobk_get_state(e->stream, (const DevParams*)e->P_dev, e->S, (f32*)nullptr, d);
-    hipError_t err = hipMemcpyAsync(host_out, d, (size_t)e->B * 8, hipMemcpyDeviceToHost, e->stream);
-    hipStreamSynchronize(e->stream);
-    hipFree(d);
-    HIPCHK(err);
-    return LOB_OK;
-}
-
-int lob_get_terminal(lob_engine* e, uint8_t* host_out) {
-    int rc = need_reset(e, "lob_get_terminal");
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(e->device));
-    std::vector<i32> done(e->B), tm(e->B);
-    HIPCHK(hipMemcpyAsync(done.data(), e->S.done, (size_t)e->B * 4, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(tm.data(), e->S.time_ms, (size_t)e->B * 4, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    for (int b = 0; b < e->B; b++) {
-        bool open = ((i64)tm[b] > e->P.open_ms + 30 * 60000LL) && ((i64)tm[b] < e->P.close_ms - 30 * 60000LL);
-        host_out[b] = done[b] == 2 ? 2 : (open ? 0 : 1);
-    }
-    return LOB_OK;
-}
-
-int lob_clear_inventory(lob_engine* e) {
-    int rc = need_reset(e, "lob_clear_inventory");
-    if (rc) return rc;
-    if ((rc = not_mid_step(e, "lob_clear_inventory"))) return rc;
-    HIPCHK(hipSetDevice(e->device));
-    lobk_clear_inventory(e->stream, (const DevParams*)e->P_dev, e->S);
-    e->hits_ok = false;
-    HIPCHK(hipGetLastError());
-    return check_device_errors(e);
-}
-
-int lob_get_books(lob_engine* e, int32_t first, int32_t n, lob_book_dump* out) {
-    if (!e || !out || first < 0 || n < 1 || first + n > e->B) { lob_set_error("lob_get_books: bad range"); return LOB_EINVAL; }
-    HIPCHK(hipSetDevice(e->device));
-    if (e->dump_cap < n) {
-        if (e->dump_dev) hipFree(e->dump_dev);
-        HIPCHK(hipMalloc((void**)&e->dump_dev, (size_t)n * sizeof(lob_book_dump)));
-        e->dump_cap = n;
-    }
-    lobk_dump(e->stream, (const DevParams*)e->P_dev, e->S, first, n, e->dump_dev);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, e->dump_dev, (size_t)n * sizeof(lob_book_dump), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return LOB_OK;
-}
-int lob_get_book(lob_engine* e, int32_t book, lob_book_dump* out) { return lob_get_books(e, book, 1, out); }
-
-// The batch's episode statistics, reduced on the device (lob_kernels.h episode_stats_partial_kernel): the kernels get the few field
-// arrays they read as arguments; n_out records come back.  Reads only.
-int lob_episode_stats(lob_engine* e, int32_t by_day, lob_episode_record* out, int32_t cap, int32_t* n_out) {
-    if (!e || !out || !n_out) { lob_set_error("lob_episode_stats: NULL argument"); return LOB_EINVAL; }
-    int rc = need_reset(e, "lob_episode_stats");
-    if (rc) return rc;
-    if ((rc = not_mid_step(e, "lob_episode_stats"))) return rc;
-    if (by_day && (!e->lib || e->lib_cur < 0)) { lob_set_error("lob_episode_stats: by_day without an episode on a day library (lob_load_days, a selection, lob_reset)"); return LOB_ESTATE; }
-    const int n = by_day ? 1 + e->lib_days : 1;
-    *n_out = n;
-    if (cap < n) { lob_set_error("lob_episode_stats: " + std::to_string(n) + " records, room for " + std::to_string(cap)); return LOB_EINVAL; }
-    HIPCHK(hipSetDevice(e->device));
-    const size_t need = (size_t)n * (1 + (size_t)lobk_stats_chunks(e->B));
-    if (e->stats_cap < need) {
-        if (e->stats_dev) hipFree(e->stats_dev);
-        e->stats_dev = nullptr; e->stats_cap = 0;
-        HIPCHK(hipMalloc((void**)&e->stats_dev, need * sizeof(lob_episode_record)));
-        e->stats_cap = need;
-    }
-    StatsSrc s;
-    s.ep_reward = e->S.ep_reward; s.ep_pnl = e->S.ep_pnl; s.ep_bandh = e->S.ep_bandh;
-    s.total_ticks = e->S.total_ticks; s.market_buys = e->S.market_buys; s.market_sells = e->S.market_sells;
-    s.done = e->S.done; s.time_ms = e->S.time_ms; s.ntr_snap = e->S.ntr_snap; s.tick_pos = e->S.tick_pos;
-    s.day = by_day ? e->lib_day[e->lib_cur] : nullptr;
-    s.open_ms = e->P.open_ms; s.close_ms = e->P.close_ms; s.book_id_offset = e->P.book_id_offset; s.B = e->B;
-    lobk_episode_stats(e->stream, s, n, e->stats_dev + n, e->stats_dev);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, e->stats_dev, (size_t)n * sizeof(lob_episode_record), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return LOB_OK;
-}
 
 // One env-step of every book (run_steps).  The books are split into EnginePlan::groups contiguous groups, each running its action
 // half (act -> env) and its learn half (memo, traces, TD errors) on its own stream; both groups only READ theta, so the
@@ -2364,151 +1143,41 @@ static int run_steps(lob_engine* e, int32_t n_steps, int mode, int half = 0) {
 }
 
 int lob_td_step(lob_engine* e, int32_t n_steps) {
-    int rc = need_reset(e, "lob_td_step");
+    int rc = guard(e, "lob_td_step", RESET);
     if (rc) return rc;
     if (n_steps < 0) return LOB_EINVAL;
     if (e->half_open) { lob_set_error("lob_td_step: a step is half done (lob_td_step_begin without lob_td_step_end)"); return LOB_ESTATE; }
-    if ((rc = not_restored(e, "lob_td_step"))) return rc;
+    LOB_GUARD(e, lob_td_step);
     return run_steps(e, n_steps, 0);
 }
 int lob_td_step_begin(lob_engine* e) {
-    int rc = need_reset(e, "lob_td_step_begin");
+    int rc = guard(e, "lob_td_step_begin", RESET);
     if (rc) return rc;
     if (e->half_open) { lob_set_error("lob_td_step_begin: the previous step has not been ended"); return LOB_ESTATE; }
-    if ((rc = not_restored(e, "lob_td_step_begin"))) return rc;
+    LOB_GUARD(e, lob_td_step_begin);
     if (e->plan.groups > 1) { lob_set_error("lob_td_step_begin: not with two book groups (LOB_GROUPS=2)"); return LOB_ESTATE; }
     return run_steps(e, 1, 0, 1);
 }
 int lob_td_split_supported(lob_engine* e) { return e && e->plan.groups == 1 ? 1 : 0; }
 int lob_td_step_end(lob_engine* e) {
-    int rc = need_reset(e, "lob_td_step_end");
+    int rc = guard(e, "lob_td_step_end", RESET);
     if (rc) return rc;
     if (!e->half_open) { lob_set_error("lob_td_step_end: no step begun"); return LOB_ESTATE; }
     return run_steps(e, 1, 0, 2);
 }
 int lob_eval_step(lob_engine* e, int32_t n_steps) {
-    int rc = need_reset(e, "lob_eval_step");
+    int rc = guard(e, "lob_eval_step", RESET);
     if (rc) return rc;
     if (n_steps < 0) return LOB_EINVAL;
     if (e->half_open) { lob_set_error("lob_eval_step: a learner step is half done"); return LOB_ESTATE; }
-    if ((rc = not_restored(e, "lob_eval_step"))) return rc;
+    LOB_GUARD(e, lob_eval_step);
     return run_steps(e, n_steps, 1);
 }
 
-int lob_model_log_enable(lob_engine* e, int32_t on) {
-    if (!e) return LOB_EINVAL;
-    HIPCHK(hipSetDevice(e->device));
-    if (on && !e->S.ml_part) {
-        int rc = dev_alloc(e, &e->S.ml_part, (size_t)LOB_ML_BLOCKS);
-        if (rc == LOB_OK) rc = dev_alloc(e, &e->S.ml_npart, (size_t)LOB_ML_BLOCKS);
-        if (rc == LOB_OK) rc = dev_alloc(e, &e->S.ml_agg, 1);
-        if (rc == LOB_OK) rc = dev_alloc(e, &e->S.ml_cnt, 2);
-        if (rc == LOB_OK) rc = dev_alloc(e, &e->S.ml_rows, (size_t)LOB_ML_ROWS);
-        if (rc != LOB_OK) return rc;
-    }
-    e->model_log = on != 0;
-    return LOB_OK;
-}
-int lob_model_log_read(lob_engine* e, double* rows, int32_t cap, int32_t* n_rows, int64_t* n_lost) {
-    if (!e || !rows || cap < 0 || !n_rows) return LOB_EINVAL;
-    *n_rows = 0;
-    if (n_lost) *n_lost = 0;
-    if (!e->S.ml_part) return LOB_OK;
-    HIPCHK(hipSetDevice(e->device));
-    i64 cnt[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(cnt, e->S.ml_cnt, sizeof cnt, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    const i64 kept = std::min<i64>(cnt[1], LOB_ML_ROWS), n = std::min<i64>(kept, cap);
-    if (n > 0) HIPCHK(hipMemcpyAsync(rows, e->S.ml_rows, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
-    // the rows are handed over once: the counter starts again (the running aggregate stays)
-    HIPCHK(hipMemsetAsync(e->S.ml_cnt + 1, 0, sizeof(i64), e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    *n_rows = (int32_t)n;
-    if (n_lost) *n_lost = cnt[1] - n;   // rows beyond the ring (LOB_ML_ROWS between two reads) or beyond `cap`
-    return LOB_OK;
-}
-
-// The step log (include/lob_engine.h): the log's memory belongs to the engine, not to DevState -- the step kernels never see it.
-int lob_step_log_enable(lob_engine* e, const int32_t* host_books, int32_t n_sel, int32_t cap_steps) {
-    if (!e) { lob_set_error("lob_step_log_enable: NULL engine"); return LOB_EINVAL; }
-    { int rc = not_mid_step(e, "lob_step_log_enable"); if (rc) return rc; }
-    HIPCHK(hipSetDevice(e->device));
-    if (n_sel == 0) {
-        HIPCHK(hipStreamSynchronize(e->stream));   // (steps still in flight write the log)
-        step_log_free(e);
-        return LOB_OK;
-    }
-    if (n_sel < 0 || n_sel > e->B || cap_steps < 1) { lob_set_error("lob_step_log_enable: n_sel outside [0, n_books] or cap_steps < 1"); return LOB_EINVAL; }
-    if (!host_books && n_sel != e->B) { lob_set_error("lob_step_log_enable: host_books == NULL selects every book: n_sel must be n_books"); return LOB_EINVAL; }
-    if (host_books)
-        for (int j = 0; j < n_sel; j++)
-            if (host_books[j] < 0 || host_books[j] >= e->B || (j > 0 && host_books[j] <= host_books[j - 1])) {
-                lob_set_error("lob_step_log_enable: the books must be strictly ascending and within [0, n_books)");
-                return LOB_EINVAL;
-            }
-    HIPCHK(hipStreamSynchronize(e->stream));
-    step_log_free(e);
-    hipError_t err = hipMalloc((void**)&e->slog_rows, (size_t)n_sel * (size_t)cap_steps * sizeof(lob_step_row));
-    if (err == hipSuccess) err = hipMalloc((void**)&e->slog_cnt, 2 * (size_t)n_sel * sizeof(i32));
-    if (err == hipSuccess && host_books) err = hipMalloc((void**)&e->slog_sel, (size_t)n_sel * sizeof(i32));
-    if (err != hipSuccess) {
-        (void)hipGetLastError();
-        step_log_free(e);
-        lob_set_error(std::string("lob_step_log_enable: hipMalloc failed: ") + hipGetErrorString(err));
-        return LOB_ENOMEM;
-    }
-    e->slog_n = n_sel; e->slog_cap = cap_steps;
-    HIPCHK(hipMemsetAsync(e->slog_cnt, 0, 2 * (size_t)n_sel * sizeof(i32), e->stream));
-    if (host_books) HIPCHK(hipMemcpyAsync(e->slog_sel, host_books, (size_t)n_sel * sizeof(i32), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));   // (host_books is the caller's again)
-    return LOB_OK;
-}
-static int step_log_on(lob_engine* e, const char* who) {
-    if (!e) { lob_set_error(std::string(who) + ": NULL engine"); return LOB_EINVAL; }
-    if (!e->slog_n) { lob_set_error(std::string(who) + ": the step log is off (lob_step_log_enable)"); return LOB_ESTATE; }
-    return not_mid_step(e, who);
-}
-int lob_step_log_counts(lob_engine* e, int32_t* n_rows, int32_t* n_lost) {
-    int rc = step_log_on(e, "lob_step_log_counts");
-    if (rc) return rc;
-    if (!n_rows) { lob_set_error("lob_step_log_counts: n_rows == NULL"); return LOB_EINVAL; }
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipMemcpyAsync(n_rows, e->slog_cnt, (size_t)e->slog_n * sizeof(i32), hipMemcpyDeviceToHost, e->stream));
-    if (n_lost) HIPCHK(hipMemcpyAsync(n_lost, e->slog_cnt + e->slog_n, (size_t)e->slog_n * sizeof(i32), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return LOB_OK;
-}
-int lob_step_log_read(lob_engine* e, int32_t first_sel, int32_t n_sel, int32_t first_row, int32_t n_rows, lob_step_row* host_out) {
-    int rc = step_log_on(e, "lob_step_log_read");
-    if (rc) return rc;
-    if (!host_out || first_sel < 0 || n_sel < 1 || n_sel > e->slog_n - first_sel || first_row < 0 || n_rows < 1 || n_rows > e->slog_cap - first_row) {
-        lob_set_error("lob_step_log_read: NULL, or a range outside the selection or cap_steps");
-        return LOB_EINVAL;
-    }
-    HIPCHK(hipSetDevice(e->device));
-    const size_t need = (size_t)n_sel * (size_t)n_rows;
-    if (e->slog_stage_cap < need) {
-        if (e->slog_stage) hipFree(e->slog_stage);
-        e->slog_stage = nullptr; e->slog_stage_cap = 0;
-        if (hipMalloc((void**)&e->slog_stage, need * sizeof(lob_step_row)) != hipSuccess) {
-            (void)hipGetLastError();
-            e->slog_stage = nullptr;
-            lob_set_error("lob_step_log_read: no room for the staging buffer (read fewer books or rows per call)");
-            return LOB_ENOMEM;
-        }
-        e->slog_stage_cap = need;
-    }
-    lobk_step_log_gather(e->stream, e->slog_rows, e->slog_cnt, e->slog_n, first_sel, n_sel, first_row, n_rows, e->slog_stage);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host_out, e->slog_stage, need * sizeof(lob_step_row), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return LOB_OK;
-}
 
 int lob_handle_terminal(lob_engine* e) {
     if (!e) return LOB_EINVAL;
-    { int rc = not_mid_step(e, "lob_handle_terminal"); if (rc) return rc; }
-    { int rc = not_restored(e, "lob_handle_terminal"); if (rc) return rc; }
+    LOB_GUARD(e, lob_handle_terminal);
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(clear_traces_kernel, dim3(grid_lanes(e->B)), dim3(256), 0, e->stream, e->S);
     HIPCHK(hipGetLastError());
@@ -2521,20 +1190,20 @@ int lob_set_epsilon(lob_engine* e, double eps) { if (!e) return LOB_EINVAL; e->P
 static int features_impl(lob_engine* e, const float* host_vars, int32_t n, int32_t* out_idx, double* out_q) {
     if (!e || !host_vars || n < 1) { lob_set_error("lob_features: bad argument"); return LOB_EINVAL; }
     HIPCHK(hipSetDevice(e->device));
-    f32* dv = nullptr; i32* di = nullptr; f64* dq = nullptr;
-    HIPCHK(hipMalloc((void**)&dv, (size_t)n * e->P.V * 4));
-    if (out_idx) HIPCHK(hipMalloc((void**)&di, (size_t)n * LOB_N_ACTIONS * 96 * 4));
-    if (out_q) HIPCHK(hipMalloc((void**)&dq, (size_t)n * LOB_N_ACTIONS * 8));
-    HIPCHK(hipMemcpyAsync(dv, host_vars, (size_t)n * e->P.V * 4, hipMemcpyHostToDevice, e->stream));
+    DevTemp<f32> dv;
+    DevTemp<i32> di;
+    DevTemp<f64> dq;
+    if (dv.alloc((size_t)n * e->P.V) || (out_idx && di.alloc((size_t)n * LOB_N_ACTIONS * 96)) || (out_q && dq.alloc((size_t)n * LOB_N_ACTIONS))) {
+        lob_set_error("lob_features: no room for the rows' device buffers");
+        return LOB_ENOMEM;
+    }
+    HIPCHK(hipMemcpyAsync(dv.p, host_vars, (size_t)n * e->P.V * 4, hipMemcpyHostToDevice, e->stream));
     hipLaunchKernelGGL(features_kernel, dim3(grid_waves(n)), dim3(LOB_BLOCK), 0, e->stream, e->P, (const f64*)e->S.theta,
-                       (const uint32_t*)e->S.theta_nz, (const uint32_t*)e->rnd_dev, (const f32*)dv, n, di, dq);
+                       (const uint32_t*)e->S.theta_nz, (const uint32_t*)e->rnd_dev, (const f32*)dv.p, n, di.p, dq.p);
     hipError_t err = hipGetLastError();
-    if (err == hipSuccess && out_idx) err = hipMemcpyAsync(out_idx, di, (size_t)n * LOB_N_ACTIONS * 96 * 4, hipMemcpyDeviceToHost, e->stream);
-    if (err == hipSuccess && out_q) err = hipMemcpyAsync(out_q, dq, (size_t)n * LOB_N_ACTIONS * 8, hipMemcpyDeviceToHost, e->stream);
-    hipStreamSynchronize(e->stream);
-    hipFree(dv);
-    if (di) hipFree(di);
-    if (dq) hipFree(dq);
+    if (err == hipSuccess && out_idx) err = hipMemcpyAsync(out_idx, di.p, (size_t)n * LOB_N_ACTIONS * 96 * 4, hipMemcpyDeviceToHost, e->stream);
+    if (err == hipSuccess && out_q) err = hipMemcpyAsync(out_q, dq.p, (size_t)n * LOB_N_ACTIONS * 8, hipMemcpyDeviceToHost, e->stream);
+    hipStreamSynchronize(e->stream);   // (the buffers are freed behind it, on every way out)
     HIPCHK(err);
     return LOB_OK;
 }
@@ -2567,7 +1236,7 @@ int lob_theta_set(lob_engine* e, int32_t which, const double* host_in, int64_t c
     f64* th; uint32_t* nz;
     int rc = theta_slot(e, which, &th, &nz);
     if (rc) return rc;
-    if ((rc = not_mid_step(e, "lob_theta_set"))) return rc;
+    LOB_GUARD(e, lob_theta_set);
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemcpyAsync(th, host_in, (size_t)count * 8, hipMemcpyHostToDevice, e->stream));
     if (e->S.theta_sync) {
@@ -2773,11 +1442,12 @@ int lob_delta_sparse_maps(lob_engine* e, int32_t world, uint32_t** dev_own, uint
     if (!lob_delta_sparse_supported(e)) { lob_set_error("lob_delta_sparse_*: needs the shared-theta fast path and lob_delta_init"); return LOB_ESTATE; }
     HIPCHK(hipSetDevice(e->device));
     const int64_t W = spx_words(e);
-    if (e->spx_world < world) {
-        if (e->spx_gather) { hipFree(e->spx_gather); e->spx_gather = nullptr; }
-        HIPCHK(hipMalloc((void**)&e->spx_gather, (size_t)world * W * 4));
-        e->spx_world = world;
+    if (e->spx_gather.reserve((size_t)world * W)) {
+        e->spx_world = 0;
+        lob_set_error("lob_delta_sparse_maps: no room for the ranks' gathered maps");
+        return LOB_ENOMEM;
     }
+    e->spx_world = std::max(e->spx_world, world);
     if (!e->spx_union) {
         // the pinned word the union's size is handed over in, and its event.  A rank without them would ask for the exact count at
         // every exchange while the others use the fixed one -- collectives of different lengths: it fails HERE instead, where a
@@ -2811,7 +1481,7 @@ int lob_delta_sparse_maps(lob_engine* e, int32_t world, uint32_t** dev_own, uint
     e->spx_buf = e->S.delta;
     e->spx_cap = e->P.M;
     *dev_own = e->S.theta_nzx;
-    *dev_gather = e->spx_gather;
+    *dev_gather = e->spx_gather.p;
     *words = W;
     return LOB_OK;
 }
@@ -2825,7 +1495,7 @@ int lob_delta_sparse_pack(lob_engine* e, int32_t world, double** dev_buf, int64_
     const int nb = (int)((W + LOB_SPX_BLOCK - 1) / LOB_SPX_BLOCK);
     {
         TimedLaunch t(e, "delta_begin_kernel", nullptr, true);
-        hipLaunchKernelGGL(sparse_union_kernel, dim3(nb), dim3(LOB_SPX_BLOCK), 0, e->stream, (const uint32_t*)e->spx_gather, (int)world, (i64)W, e->spx_union, e->spx_block_cnt);
+        hipLaunchKernelGGL(sparse_union_kernel, dim3(nb), dim3(LOB_SPX_BLOCK), 0, e->stream, (const uint32_t*)e->spx_gather.p, (int)world, (i64)W, e->spx_union, e->spx_block_cnt);
         hipLaunchKernelGGL(sparse_scan_kernel, dim3(1), dim3(1024), 0, e->stream, (const i32*)e->spx_block_cnt, nb, e->spx_block_off, e->spx_total);
     }
     // the union's size of the exchange BEFORE this one (its copy to pinned memory has had a whole exchange interval to land)
@@ -2944,53 +1614,19 @@ extern "C" int lob_debug_prof(lob_engine* e, int64_t out[LOB_PROF_N]) {
 extern "C" int lob_debug_fastpath(lob_engine* e, int64_t* out, int32_t n_out) {
     if (!e || !out || n_out < 4 + LOB_FP_BINS) return LOB_EINVAL;
     HIPCHK(hipSetDevice(e->device));
-    i64* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, (size_t)(4 + LOB_FP_BINS) * 8));
-    hipError_t err = hipMemsetAsync(d, 0, (size_t)(4 + LOB_FP_BINS) * 8, e->stream);
+    DevTemp<i64> d;
+    if (d.alloc(4 + LOB_FP_BINS)) { lob_set_error("lob_debug_fastpath: no room for the counts"); return LOB_ENOMEM; }
+    hipError_t err = hipMemsetAsync(d.p, 0, (size_t)(4 + LOB_FP_BINS) * 8, e->stream);
     if (err == hipSuccess) {
-        hipLaunchKernelGGL(fastpath_stats_kernel, dim3(512), dim3(256), 0, e->stream, e->S, (i64)e->P.M, e->P.memo ? 1 : 0, d);
+        hipLaunchKernelGGL(fastpath_stats_kernel, dim3(512), dim3(256), 0, e->stream, e->S, (i64)e->P.M, e->P.memo ? 1 : 0, d.p);
         err = hipGetLastError();
     }
-    if (err == hipSuccess) err = hipMemcpyAsync(out, d, (size_t)(4 + LOB_FP_BINS) * 8, hipMemcpyDeviceToHost, e->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(out, d.p, (size_t)(4 + LOB_FP_BINS) * 8, hipMemcpyDeviceToHost, e->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    hipFree(d);
     HIPCHK(err);
     return LOB_OK;
 }
 
-// Diagnostics (not part of include/lob_engine.h): learner steps (combined update) since lob_create by the shape of their update
-// -- [0] updates added to their slots by the learn / trace kernels, accumulate_kernel over the list they left (Q(lambda)),
-// [1] steps whose learn_q_rest_kernel ran beside the trace kernels on the second stream, [2] accumulate_block_kernel,
-// [3] accumulate_kernel over every book; steps with the action selection inside the env kernel (launch_env_fused): [4] books without a
-// usable hit list served in-kernel (act_book), [5] through the work list to the wave-per-book act kernel because the learn
-// kernels' hand-back count said most books have none (a dense theta), [6] through the work list for another reason (the first
-// step on lists, LOB_INLINE_GENERAL=0); [7] of the steps counted under [2], those whose sums went through the dense ids
-// (accumulate_dense_kernel).  The tests use it to know which path they have compared with the oracle.
-extern "C" int lob_debug_flow(lob_engine* e, int64_t out[8]) {
-    if (!e || !out) return LOB_EINVAL;
-    for (int i = 0; i < 8; i++) out[i] = e->flow[i];
-    return LOB_OK;
-}
-
-// Diagnostics (not part of include/lob_engine.h): launches since lob_create of kernels that share a timer name ("env_kernel",
-// "learn_kernel") -- [0] env_step_kernel, [1] env_step16_kernel (which of the two: lobk_env_step says), [2] the fused
-// env_kernel<., ., 1>, [3] learn_q_pair_kernel, [4] learn_q_lane_kernel, [5] learn_q_fast_kernel.  Host counters; the tests use
-// them to show which kernel a case has compared with the oracle.
-extern "C" int lob_debug_launches(lob_engine* e, int64_t out[6]) {
-    if (!e || !out) return LOB_EINVAL;
-    for (int i = 0; i < 6; i++) out[i] = e->launched[i];
-    return LOB_OK;
-}
-
-// Diagnostics (not part of include/lob_engine.h): learner steps since lob_create that [0] read the learn kernels' hand-back count
-// (the hint of LOB_HINT_LAG steps ago), [1] of those, steps whose hint word had not arrived within the spin limit and that went by
-// a count of 0 instead -- the path such a step took was chosen by the host's timing, not by the run.
-extern "C" int lob_debug_hint(lob_engine* e, int64_t out[2]) {
-    if (!e || !out) return LOB_EINVAL;
-    out[0] = e->hint_reads;
-    out[1] = e->hint_misses;
-    return LOB_OK;
-}
 
 // Diagnostics (not part of include/lob_engine.h): books whose action came from act_light_kernel so far, and the step id of
 // the last update that voided the hit lists (-1: never).
@@ -3007,13 +1643,6 @@ extern "C" int lob_debug_light(lob_engine* e, int64_t out[2]) {
     return LOB_OK;
 }
 
-// Diagnostics (not part of include/lob_engine.h): sparse exchanges without / with a host synchronisation, exchanges whose union outgrew
-// the fixed count (their surplus travelled one exchange later), the fixed count, the last union size known to the host.
-extern "C" int lob_debug_exchange(lob_engine* e, int64_t out[5]) {
-    if (!e || !out) return LOB_EINVAL;
-    out[0] = e->spx_nosync; out[1] = e->spx_synced; out[2] = e->spx_overflows; out[3] = e->spx_fixed; out[4] = e->spx_last_total;
-    return LOB_OK;
-}
 
 // Diagnostics (not part of include/lob_engine.h): generations without a combine slot that trace_rest_kernel left to apply_kernel so far.
 extern "C" int lob_debug_deferred(lob_engine* e, int64_t out[1]) {

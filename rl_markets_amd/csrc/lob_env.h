@@ -68,7 +68,7 @@ LOB_HD void drec_from_abi(const uint32_t* src, int D, int T, uint32_t* dst) {
 // 16-byte loads are issued unconditionally -- a load under a branch on D splits the batch of loads it belongs to (the
 // compiler waits for everything in flight at the join), and these kernels are chains of memory round trips.  For D <= 8 the
 // last quad lies in the next array of the record, after the last array in the trade slots / the next record: read and
-// masked out (the stream buffer is allocated with a tail pad, lob_engine.hip set_records).
+// masked out (the stream buffer is allocated with a tail pad, lob_tu_host_streams.hip set_records).
 #define LOB_LEVEL_QUADS ((LOB_MAX_DEPTH + 3) / 4)
 __device__ inline void drec_unpack(const uint4* v, int D, uint32_t* out) {
 #pragma unroll

@@ -1,5 +1,7 @@
 // Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is fourteen
-// .hip files built in parallel: lob_engine.hip -- the C ABI's host side and the update / memo / trace kernels --, lob_tu_env.hip,
+// .hip files with kernels, built in parallel with three that hold host code only -- lob_tu_host_streams.hip, lob_tu_host_vec.hip,
+// lob_tu_host_reads.hip: the C ABI's families that launch through this header alone, lob_engine_impl.h --: lob_engine.hip -- the
+// engine object, the step pipeline, the weights and the update / memo / trace kernels --, lob_tu_env.hip,
 // lob_tu_prepass.hip, lob_tu_learn.hip, lob_tu_stats.hip, lob_tu_steplog.hip, lob_tu_vec.hip, lob_tu_vecbook.hip, lob_tu_vechist.hip, lob_tu_snapshot.hip,
 // lob_tu_vecact.hip, lob_tu_vecfeat.hip, lob_tu_vecpeek.hip, lob_tu_vecroll.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
 // lob_engine.hip used when it held the launches itself.  Kernels measured and lost (NOTES.md "Round 4") are only compiled with

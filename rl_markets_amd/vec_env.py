@@ -122,16 +122,30 @@ class VecEnv:
         # (the zero fills above ran on torch's stream: the engine's first write must come after them)
         self.stream.wait_stream(torch.cuda.current_stream(dev))
 
-    def _call(self, fn, *args):
+    def _on_engine(self, fn, *args, inputs=()):
+        """The hand-off between torch's current stream and the engine's, around one engine call; `inputs`: the caller's tensors the
+        engine reads (None entries are skipped).  Output tensors are allocated or zero-filled before this is called."""
         cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)      # what torch has enqueued so far (the actions) comes first
+        self.stream.wait_stream(cur)      # what torch has enqueued so far (the inputs, the zero fills, readers of the last outputs) comes first
+        fn(*args)
+        cur.wait_stream(self.stream)      # what torch enqueues from here on sees the outputs
+        # The engine reads the inputs on its own stream, and the caching allocator must not hand their blocks out again before
+        # that.  `cur` now waits for the engine's stream, so whatever follows on `cur` follows the read: the blocks are marked as
+        # used on `cur` (nothing to do where they were allocated there), never on the engine's stream, which the allocator would
+        # record an event on when a tensor is freed -- possibly after Engine.close() has destroyed that stream.
+        for t in inputs:
+            if t is not None:
+                t.record_stream(cur)
+
+    def _observing(self, fn, *args):
         fn(*args, self.out)
         if self.book_out is not None:
             self.eng.vec_book(self.book_out)   # (right behind it on the engine's stream: the book as the step left it)
         if self.hist_out is not None:
             self.eng.vec_history(self.history, self.hist_out)
-        cur.wait_stream(self.stream)      # what torch enqueues from here on sees the outputs
-        return cur
+
+    def _call(self, fn, *args, inputs=()):
+        self._on_engine(self._observing, fn, *args, inputs=inputs)
 
     def reset(self):
         """lob_reset (which waits for its own result, as it always has) and the first observation."""
@@ -147,12 +161,7 @@ class VecEnv:
         """actions: int32 [B] on the engine's device.  Returns (obs, reward, terminal, stepped), the persistent tensors."""
         if actions.dtype != torch.int32 or not actions.is_cuda or actions.shape != (self.B,) or not actions.is_contiguous():
             raise ValueError("VecEnv.step: actions must be a contiguous int32 CUDA tensor of shape (%d,)" % self.B)
-        cur = self._call(self.eng.vec_step, actions.data_ptr())
-        # The engine reads `actions` on its own stream, and the caching allocator must not hand the block out again before
-        # that.  `cur` now waits for the engine's stream, so whatever follows on `cur` follows the read: the block is marked as
-        # used on `cur` (nothing to do where it was allocated there), never on the engine's stream, which the allocator would
-        # record an event on when the tensor is freed -- possibly after Engine.close() has destroyed that stream.
-        actions.record_stream(cur)
+        self._call(self.eng.vec_step, actions.data_ptr(), inputs=(actions,))
         return self.obs, self.reward, self.terminal, self.stepped
 
     _ACT_MODES = {"greedy": abi.ACT_GREEDY, "behaviour": abi.ACT_BEHAVIOUR, "argmax": abi.ACT_ARGMAX}
@@ -163,14 +172,11 @@ class VecEnv:
         own policy streams, as eval_step / td_step do; "argmax" draws nothing."""
         if mode not in self._ACT_MODES:
             raise ValueError("VecEnv.act: mode must be one of %s" % ", ".join(sorted(self._ACT_MODES)))
-        cur = torch.cuda.current_stream(self.device)
         if self.act_out is None:
             self.act_actions = torch.zeros(self.B, dtype=torch.int32, device=self.device)
             self.act_q = torch.zeros((self.B, abi.LOB_N_ACTIONS), dtype=torch.float64, device=self.device)
             self.act_out = abi.VecActOut(self.act_actions.data_ptr(), self.act_q.data_ptr())
-        self.stream.wait_stream(cur)      # (the zero fills, and whoever still reads the tensors of the last act())
-        self.eng.vec_act(self._ACT_MODES[mode], self.act_out)
-        cur.wait_stream(self.stream)
+        self._on_engine(self.eng.vec_act, self._ACT_MODES[mode], self.act_out)
         return self.act_actions
 
     def peek(self, actions=None):
@@ -192,7 +198,6 @@ class VecEnv:
                 mask |= 1 << int(a)
             if mask == 0:
                 raise ValueError("VecEnv.peek: no action given")
-        cur = torch.cuda.current_stream(self.device)
         if self.peek_out is None:
             n = abi.LOB_N_ACTIONS
             self.peek_obs = torch.zeros((n, self.B, self.V), dtype=torch.float32, device=self.device)
@@ -201,9 +206,7 @@ class VecEnv:
             self.peek_stepped = torch.zeros((n, self.B), dtype=torch.int32, device=self.device)
             self.peek_out = abi.VecPeekOut(self.peek_obs.data_ptr(), self.peek_reward.data_ptr(), self.peek_terminal.data_ptr(),
                                            self.peek_stepped.data_ptr())
-        self.stream.wait_stream(cur)      # (the zero fills, and whoever still reads the tensors of the last peek())
-        self.eng.vec_peek(mask, self.peek_out)
-        cur.wait_stream(self.stream)
+        self._on_engine(self.eng.vec_peek, mask, self.peek_out)
         return self.peek_obs, self.peek_reward, self.peek_terminal, self.peek_stepped
 
     def rollout(self, plans, gamma=1.0):
@@ -238,26 +241,16 @@ class VecEnv:
         terminal = torch.empty((P, self.B), dtype=torch.uint8, device=self.device)
         stepped = torch.empty((P, self.B), dtype=torch.int32, device=self.device)
         ret = torch.empty((P, self.B), dtype=torch.float64, device=self.device)
-        cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)      # the plans are ready
-        self.eng.vec_rollout(plans.data_ptr(), P, H, gamma,
-                             abi.VecRolloutOut(obs.data_ptr(), reward.data_ptr(), terminal.data_ptr(), stepped.data_ptr(), ret.data_ptr()))
-        cur.wait_stream(self.stream)
-        plans.record_stream(cur)          # (as step() does with the actions)
+        out = abi.VecRolloutOut(obs.data_ptr(), reward.data_ptr(), terminal.data_ptr(), stepped.data_ptr(), ret.data_ptr())
+        self._on_engine(self.eng.vec_rollout, plans.data_ptr(), P, H, gamma, out, inputs=(plans,))
         return obs, reward, terminal, stepped, ret
 
     def q_values(self, vars):
         """lob_vec_q: Q(s, .) under the engine's weights (theta; book 0's under private theta) for n free-standing states, f32 [n, V]
         on the engine's device -> a new f64 [n, 9] tensor; bit for bit Engine.q_values of the same rows."""
-        if (not isinstance(vars, torch.Tensor) or vars.dtype != torch.float32 or not vars.is_cuda or vars.device != self.device
-                or vars.dim() != 2 or vars.shape[1] != self.V or vars.shape[0] < 1 or not vars.is_contiguous()):
-            raise ValueError("VecEnv.q_values: vars must be a contiguous float32 CUDA tensor of shape (n, %d) on the engine's device" % self.V)
-        q = torch.empty((vars.shape[0], abi.LOB_N_ACTIONS), dtype=torch.float64, device=self.device)
-        cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)      # the rows are ready
-        self.eng.vec_q(vars.data_ptr(), vars.shape[0], q.data_ptr())
-        cur.wait_stream(self.stream)
-        vars.record_stream(cur)           # (as step() does with the actions)
+        n = self._rows(vars, "q_values")
+        q = torch.empty((n, abi.LOB_N_ACTIONS), dtype=torch.float64, device=self.device)
+        self._on_engine(self.eng.vec_q, vars.data_ptr(), n, q.data_ptr(), inputs=(vars,))
         return q
 
     @property
@@ -295,14 +288,8 @@ class VecEnv:
         else:
             sums = torch.empty((n, abi.N_TILES), dtype=torch.int32, device=self.device)
         idx = None if actions is None else torch.empty((n, abi.N_TILES), dtype=torch.int32, device=self.device)
-        cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)      # the rows and actions are ready (and whoever still reads .feat_sums is done)
-        self.eng.vec_features(None if vars is None else vars.data_ptr(), n, None if actions is None else actions.data_ptr(),
-                              abi.VecFeatOut(sums.data_ptr(), None if idx is None else idx.data_ptr()))
-        cur.wait_stream(self.stream)
-        for t in (vars, actions):
-            if t is not None:
-                t.record_stream(cur)      # (as step() does with the actions)
+        self._on_engine(self.eng.vec_features, None if vars is None else vars.data_ptr(), n, None if actions is None else actions.data_ptr(),
+                        abi.VecFeatOut(sums.data_ptr(), None if idx is None else idx.data_ptr()), inputs=(vars, actions))
         return sums if actions is None else (sums, idx)
 
     def tile_index(self, sums, actions):
@@ -319,13 +306,8 @@ class VecEnv:
         n = self.B if vars is None else self._rows(vars, "update")
         self._vec(step, torch.float64, n, "update", "step")
         self._vec(actions, torch.int32, n, "update", "actions")
-        cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)      # the steps, actions and rows are ready
-        self.eng.vec_update(None if vars is None else vars.data_ptr(), n, actions.data_ptr(), step.data_ptr(), second)
-        cur.wait_stream(self.stream)
-        for t in (step, actions, vars):
-            if t is not None:
-                t.record_stream(cur)      # (as step() does with the actions)
+        self._on_engine(self.eng.vec_update, None if vars is None else vars.data_ptr(), n, actions.data_ptr(), step.data_ptr(), second,
+                        inputs=(step, actions, vars))
 
     def _mask_ptr(self, mask, who):
         if mask is None:
@@ -339,12 +321,7 @@ class VecEnv:
         """lob_snapshot_save: the environment state of the selected books (mask None: all, which (re)starts the slot) into `slot`.
         The slot's first save allocates its buffer and with that synchronises the device; later ones only enqueue."""
         ptr = self._mask_ptr(mask, "save")
-        cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)      # the mask is ready
-        self.eng.snapshot_save(slot, ptr)
-        cur.wait_stream(self.stream)
-        if mask is not None:
-            mask.record_stream(cur)       # (as step() does with the actions)
+        self._on_engine(self.eng.snapshot_save, slot, ptr, inputs=(mask,))
 
     def _restore_observe(self, slot, ptr, out):
         self.eng.snapshot_restore(slot, ptr)
@@ -354,9 +331,7 @@ class VecEnv:
         """lob_snapshot_restore of the selected books from `slot`, then the observation (and the book / history tensors) of the
         batch as it now stands.  Returns obs."""
         ptr = self._mask_ptr(mask, "restore")
-        cur = self._call(self._restore_observe, slot, ptr)
-        if mask is not None:
-            mask.record_stream(cur)
+        self._call(self._restore_observe, slot, ptr, inputs=(mask,))
         return self.obs
 
     def status(self):

@@ -98,3 +98,17 @@ def test_ticks_hint_equals_to_ticks(tmp_path):
                            os.path.join(ROOT, "rl_markets_amd", "csrc", "lob_host.cpp")])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and "ticks_diff OK" in out.stdout, out.stdout[-1500:]
+
+
+def test_device_buffer_owners_under_a_failing_allocator(tmp_path):
+    """The engine's grow-only device buffer and its per-call temporary (rl_markets_amd/csrc/lob_devbuf.h) take their allocator as a
+    parameter.  tests/host_env/devbuf_test.cpp drives them over one that counts live blocks and fails the k-th allocation, under
+    the address and undefined-behaviour sanitizers: a failed growth leaves pointer and capacity null and 0, the same need then
+    allocates again and succeeds, need <= capacity never reaches the allocator, a release after a failed growth frees nothing
+    twice, the temporary leaves no block behind on any way out (the second of three allocations failing among them), and no
+    block is live at exit."""
+    exe = str(tmp_path / "devbuf_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe,
+                           os.path.join(ROOT, "tests", "host_env", "devbuf_test.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "devbuf_test OK" in out.stdout, out.stdout[-1500:] + out.stderr[-3000:]

@@ -44,7 +44,7 @@ p = engine.default_params()
 p.depth, p.max_trades, p.algo, p.theta_mode = DEPTH, TRADES, abi.ALGO_QLAMBDA, abi.THETA_SHARED
 g = engine.default_gen_params()
 g.n_events = 64 + 6 * (STEPS + WARM)
-# The arrays of a snapshot (lob_engine.hip snap_prepare): 20 + 2 x 2 arrays of 4-byte and 26 + 2 x 3 of 8-byte elements [B] (the fields
+# The arrays of a snapshot (lob_tu_host_vec.hip snap_prepare): 20 + 2 x 2 arrays of 4-byte and 26 + 2 x 3 of 8-byte elements [B] (the fields
 # of LOB_ENV_FIELDS; cnt / head and sum / mean / s of the two rolling means), two rings [lb_pnl][B] of 8 bytes, and the per-book
 # records: four 4-byte words and one 8-byte word of the step header, 64 bytes of state vector.
 W = int(p.lb_pnl)
