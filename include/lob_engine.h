@@ -676,6 +676,55 @@ typedef struct lob_vec_rollout_out {   /* device pointers; NULL = not wanted, no
 int lob_vec_rollout(lob_engine* e, const int32_t* dev_actions /* [P][H][B] */, int n_plans, int horizon,
                     double gamma, const lob_vec_rollout_out* out);
 
+/* ---- vector-env interface: branches, private copies of the books stepped in a loop ---
+ * The two look-aheads above are open loop: every action must be known before the launch.  A BRANCH SET lets the imagined worlds persist
+ * between launches: n_branches private copies of every book's agent-side environment state (the per-book scalars, the two PnL
+ * windows, the observation of the last completed step), all reading the same market track, stepped one step at a time with actions
+ * from device memory and rearranged on the device -- closed-loop returns under any policy (lob_vec_q on the branches' obs continues
+ * a plan under the engine's own weights), beam search, particle resampling, tree expansion that keeps only what it selects.  One
+ * set per engine; no snapshot slot is taken.
+ *   lob_branch_out: where results go, DEVICE pointers on the engine's GPU, written in stream order; a NULL member is skipped.  Every
+ * tensor is branch-major: plane n = elements [n * n_books, (n + 1) * n_books).
+ *   lob_branch_fork (re)makes the set: every branch (n, b), n < n_branches, becomes a copy of book b's present environment state.
+ * out, when given: the observation of the book's last completed step, lob_get_terminal's value, reward +0.0, stepped 0, in every
+ * plane.  The first fork allocates the set (416 bytes per branch and book rounded up to 64 books, plus 16 * lb_pnl when the reward is
+ * LOB_REWARD_NORMED), and so does a fork that needs a larger one than any before it: allocation and release synchronise the device.
+ * Every other fork only enqueues one launch.
+ *   lob_branch_step: imagine the engine's books were in branch n's state and lob_vec_step were called with dev_actions[n][:].  Bit
+ * for bit, obs / reward / terminal / stepped at [n][b] are what that call would write, and the branch's state becomes what that call
+ * would leave behind.  The rules of the step are lob_vec_rollout's: a branch steps only if its terminal is 0 at entry; a branch that
+ * is over, or a step that runs out of data, gives reward +0.0, stepped 0 and keeps the obs of the last completed step (a step that
+ * ran dry keeps its consumed events: terminal 2); an action outside [0, LOB_N_ACTIONS) leaves the branch as it is and is NOT counted
+ * in the word lob_vec_status reports: -1 steps a subset.  h calls with a_0 .. a_{h-1} give, per step, the rewards of lob_vec_rollout
+ * under that plan and, behind the last, its obs and terminal.
+ *   lob_branch_select: branch (n, b) becomes a copy of branch (dev_parent[n][b], b) as it stood before the call; a parent outside
+ * [0, n_branches) means "keep yourself"; many children of one parent are the point.  It goes through a second buffer of the set's
+ * size, allocated by the first select (and by the first select after the set has grown): that one synchronises the device, every
+ * other select only enqueues one launch.  out, when given: obs and terminal of the new arrangement; reward and stepped are not written.
+ *   lob_branch_close releases both buffers and synchronises the device; lob_destroy does the same.
+ *   Nothing of the engine changes, as under lob_vec_peek: no book, no PnL window, no state vector, no step header, no memo / verdict /
+ * hit-list word, no counter, no step number, no step-log row, no random stream, no snapshot slot; with the same exception, the engine's
+ * sticky error word.  The branches read only the track and the records, which do not change within an episode: they stay valid while
+ * the real books step on and across lob_snapshot_save / lob_snapshot_restore.  lob_reset voids the set (the buffers stay): step and
+ * select then return LOB_ESTATE until the next fork.
+ *   All work is enqueued on the engine's stream (lob_stream) and nothing is read back.  Allowed after lob_snapshot_restore and while
+ * the step log records.  Refusals carry a message naming the call, and a refused call writes nothing.  LOB_EINVAL: a NULL engine; NULL
+ * dev_actions or dev_parent; NULL out for lob_branch_step; n_branches outside 1 .. LOB_MAX_BRANCHES.  LOB_ESTATE: before the first
+ * lob_reset, between lob_td_step_begin and lob_td_step_end, on a stream whose market track is a ring, and -- step and select -- with
+ * no live set.  LOB_ENOMEM: a buffer does not fit (the message gives its bytes).  All members NULL: fork and select still act on the
+ * set and step still steps; nothing is written to the caller. */
+#define LOB_MAX_BRANCHES 64
+typedef struct lob_branch_out {      /* device pointers on the engine's GPU; NULL = not wanted, not written */
+    float*   obs;        /* [N][B][V] */
+    double*  reward;     /* [N][B]    */
+    uint8_t* terminal;   /* [N][B]    */
+    int32_t* stepped;    /* [N][B]    */
+} lob_branch_out;
+int lob_branch_fork  (lob_engine* e, int n_branches, const lob_branch_out* out /* may be NULL */);
+int lob_branch_step  (lob_engine* e, const int32_t* dev_actions /* [N][B] */, const lob_branch_out* out);
+int lob_branch_select(lob_engine* e, const int32_t* dev_parent  /* [N][B] */, const lob_branch_out* out /* may be NULL */);
+int lob_branch_close (lob_engine* e);
+
 /* ---- episode statistics of the whole batch ---------------------------------
  * What the reference logs about ONE environment after an episode -- the `training_log` row of Runner::RunEpisode
  * (src/experiment/serial.cpp:81-88: getEpisodeReward, getEpisodePnL, total_ticks), Base::writeStats and getTotalTransactions

@@ -205,6 +205,16 @@ class VecRolloutOut(C.Structure):
     _fields_ = [("obs", C.c_void_p), ("reward", C.c_void_p), ("terminal", C.c_void_p), ("stepped", C.c_void_p), ("ret", C.c_void_p)]
 
 
+# lob_branch_*: the most branches of a set (LOB_MAX_BRANCHES)
+MAX_BRANCHES = 64
+
+
+class BranchOut(C.Structure):
+    """lob_branch_out: where lob_branch_fork / _step / _select write, four DEVICE addresses (0 = not wanted) of branch-major tensors:
+    obs f32 [N, B, V], reward f64 [N, B], terminal uint8 [N, B], stepped int32 [N, B]."""
+    _fields_ = [("obs", C.c_void_p), ("reward", C.c_void_p), ("terminal", C.c_void_p), ("stepped", C.c_void_p)]
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LOB_ENGINE_LIB: an experiment build of the same library (tools/exp_prof.py, tools/exp_variants.sh)
 LIB_PATH = os.environ.get("LOB_ENGINE_LIB") or os.path.join(_HERE, "csrc", "liblob_engine.so")
@@ -282,6 +292,10 @@ def load():
         "lob_vec_update": (C.c_int, [vp, vp, C.c_int32, vp, vp, C.c_int32]),
         "lob_vec_peek": (C.c_int, [vp, C.c_uint32, P(VecPeekOut)]),
         "lob_vec_rollout": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_double, P(VecRolloutOut)]),
+        "lob_branch_fork": (C.c_int, [vp, C.c_int, P(BranchOut)]),
+        "lob_branch_step": (C.c_int, [vp, vp, P(BranchOut)]),
+        "lob_branch_select": (C.c_int, [vp, vp, P(BranchOut)]),
+        "lob_branch_close": (C.c_int, [vp]),
         "lob_snapshot_save": (C.c_int, [vp, C.c_int32, C.c_void_p]),
         "lob_snapshot_restore": (C.c_int, [vp, C.c_int32, C.c_void_p]),
         "lob_snapshot_free": (C.c_int, [vp, C.c_int32]),

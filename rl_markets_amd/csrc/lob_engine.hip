@@ -1,6 +1,6 @@
 // Host side of the C ABI (include/lob_engine.h), the part that launches kernels of this unit by name: the engine object's life
 // (lob_create / lob_destroy / lob_reset), the step pipeline, the weights and both weight exchanges, kernel timing, the
-// diagnostics that launch.  gfx950 only; there is no CPU execution path in this file.  (One of the library's fourteen units with
+// diagnostics that launch.  gfx950 only; there is no CPU execution path in this file.  (One of the library's fifteen units with
 // kernels, lob_launch.h -- the update, memo and trace kernels are compiled here --; the streams, the vector env with the
 // snapshots, and the read-backs and logs are host-only units of their own, lob_tu_host_*.hip, over lob_engine_impl.h.)
 #define LOB_TU_SPLIT 1
@@ -602,6 +602,7 @@ void lob_destroy(lob_engine* e) {
     for (auto& b : e->snap_buf) b.release();
     if (e->snap_tab) hipFree(e->snap_tab);
     e->roll_ws.release();
+    for (auto& b : e->branch_buf) b.release();
     e->spx_gather.release();
     if (e->spx_ev) hipEventDestroy(e->spx_ev);
     if (e->spx_total_host) hipHostFree(e->spx_total_host);
@@ -719,6 +720,7 @@ int lob_reset(lob_engine* e) {
     e->rest_recent = 0;
     e->half_open = false;  // (a step begun before the reset -- e.g. an exchange that failed between the halves -- is abandoned with the episode)
     for (bool& v : e->snap_valid) v = false;   // a snapshot belongs to the episode it was taken in (the buffers stay)
+    e->branch_live = false;                    // ... and so does a branch set
     e->restored = false;
     return check_device_errors(e);
 }

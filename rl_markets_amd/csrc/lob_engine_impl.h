@@ -1,7 +1,7 @@
 // The engine object and what the host-side translation units share (private: include/lob_engine.h is the interface).  The host side
 // of the C ABI is four units: lob_engine.hip -- create / destroy / reset, the step pipeline, the weights and everything else that
 // launches a kernel of its own by name --, lob_tu_host_streams.hip (event streams and the day library), lob_tu_host_vec.hip
-// (lob_step, lob_vec_*, lob_snapshot_*) and lob_tu_host_reads.hip (read-backs, episode statistics, the logs, host counters).  The
+// (lob_step, lob_vec_*, lob_branch_*, lob_snapshot_*) and lob_tu_host_reads.hip (read-backs, episode statistics, the logs, host counters).  The
 // last three hold no kernel: they launch through lob_launch.h.
 #ifndef LOB_ENGINE_IMPL_H
 #define LOB_ENGINE_IMPL_H
@@ -207,6 +207,13 @@ struct lob_engine {
     i32* actions_dev = nullptr;
     lob::DevBuf<f64> roll_ws;   // lob_vec_rollout: the PnL windows' entries the plans push (lob_launch.h RolloutSrc::shadow), made by the first
                                 // call that needs it, grown when a later call needs more, never per call
+    // lob_branch_*: the branch set (lob_branch.h) and the buffer lob_branch_select gathers into -- the two swap roles with every
+    // select --, each made by the first call that needs it and grown only by a fork that needs more; the shape of the live set, and
+    // whether it belongs to the current episode (lob_reset clears it)
+    lob::DevBuf<char> branch_buf[2];
+    int branch_cur = 0;         // which of the two holds the set
+    int branch_n = 0;           // branches of the live set
+    bool branch_live = false;
     u64* vec_bad = nullptr;     // lob_vec_step: actions out of range since the last lob_vec_status / lob_reset (one device word)
     i32* vec_upd_tag = nullptr; // lob_vec_update: the number of the last launch that wrote a weight (one device word; lob_launch.h VecFeatSrc)
     i32 vec_upd_launch = 0;     // ... and the number of the last launch (never 0 once used)
@@ -264,6 +271,7 @@ constexpr unsigned lob_step = RESET | WHOLE_STEP;
 constexpr unsigned lob_vec_step = RESET | WHOLE_STEP, lob_vec_observe = RESET | WHOLE_STEP;
 constexpr unsigned lob_vec_book = RESET | WHOLE_STEP, lob_vec_history = RESET | WHOLE_STEP, lob_vec_act = RESET | WHOLE_STEP;
 constexpr unsigned lob_vec_peek = RESET | WHOLE_STEP | NO_RING, lob_vec_rollout = RESET | WHOLE_STEP | NO_RING;
+constexpr unsigned lob_branch_fork = RESET | WHOLE_STEP | NO_RING, lob_branch_step = RESET | WHOLE_STEP | NO_RING, lob_branch_select = RESET | WHOLE_STEP | NO_RING;
 constexpr unsigned lob_vec_features = WHOLE_STEP, lob_vec_update = WHOLE_STEP;   // (+ RESET behind it when the rows are the books')
 constexpr unsigned lob_snapshot_save = RESET | WHOLE_STEP | NO_RING_BACK, lob_snapshot_restore = RESET | WHOLE_STEP | NO_RING_BACK;
 constexpr unsigned lob_get_state = RESET, lob_get_reward = RESET, lob_get_terminal = RESET;

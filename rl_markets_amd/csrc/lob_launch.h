@@ -1,9 +1,9 @@
-// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is fourteen
+// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is fifteen
 // .hip files with kernels, built in parallel with three that hold host code only -- lob_tu_host_streams.hip, lob_tu_host_vec.hip,
 // lob_tu_host_reads.hip: the C ABI's families that launch through this header alone, lob_engine_impl.h --: lob_engine.hip -- the
 // engine object, the step pipeline, the weights and the update / memo / trace kernels --, lob_tu_env.hip,
 // lob_tu_prepass.hip, lob_tu_learn.hip, lob_tu_stats.hip, lob_tu_steplog.hip, lob_tu_vec.hip, lob_tu_vecbook.hip, lob_tu_vechist.hip, lob_tu_snapshot.hip,
-// lob_tu_vecact.hip, lob_tu_vecfeat.hip, lob_tu_vecpeek.hip, lob_tu_vecroll.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
+// lob_tu_vecact.hip, lob_tu_vecfeat.hip, lob_tu_vecpeek.hip, lob_tu_vecroll.hip, lob_tu_branch.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
 // lob_engine.hip used when it held the launches itself.  Kernels measured and lost (NOTES.md "Round 4") are only compiled with
 // -DLOB_EXPERIMENTS (tools/exp_variants.sh); a product build answers LOB_EXPERIMENTS-only requests with the product kernel.
 #ifndef LOB_LAUNCH_H
@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lob_state.h"
+#include "lob_branch.h"
 
 struct EnvFuse {  // env_kernel MODE 1 / 2, env_step_kernel (lob_kernels.h)
     const i32* list;
@@ -250,6 +251,27 @@ struct RolloutSrc {
 };
 // vec_rollout_kernel<t2>: n_plans * Bpad / 64 one-wave blocks; `t2` as lobk_env's
 void lobk_vec_rollout(hipStream_t st, bool t2, const DevParams* Pd, const DevState& S, const RolloutSrc& a);
+
+// ---- lob_tu_branch.hip ----
+// What lob_branch_fork / lob_branch_step / lob_branch_select (include/lob_engine.h) take beyond the parameters and the state, which
+// branch_fork_kernel and branch_step_kernel receive as env_kernel does (branch_select_kernel: the parameters only): the set the launch
+// writes (lob_branch.h: base, lanes, ring lengths), for a select the buffer it gathers from, the caller's [N][B] words -- actions for
+// a step, parents for a select --, the batch and its size rounded up to whole waves -- block i of the step and select grids is branch
+// i / (Bpad / 64) over the books 64 * (i % (Bpad / 64)) ... -- and the caller's device buffers, branch-major planes.
+struct BranchSrc {
+    BranchSet set;         // fork, step: the live buffer; select: the buffer that becomes the live one
+    BranchSet from;        // select: the live buffer as it stands (fork, step: unused)
+    const i32* index;      // step: actions [N][B]; select: parents [N][B]; fork: unused
+    i32 B, Bpad;           // books; B rounded up to a multiple of 64
+    i32 n_branches;
+    lob_branch_out out;    // obs [N][B][V], reward [N][B], terminal [N][B], stepped [N][B]; NULL: not wanted
+};
+// branch_fork_kernel: Bpad / 64 one-wave blocks, a lane per book writing its N copies
+void lobk_branch_fork(hipStream_t st, const DevParams* Pd, const DevState& S, const BranchSrc& a);
+// branch_step_kernel<t2>: n_branches * Bpad / 64 one-wave blocks; `t2` as lobk_env's
+void lobk_branch_step(hipStream_t st, bool t2, const DevParams* Pd, const DevState& S, const BranchSrc& a);
+// branch_select_kernel: n_branches * Bpad / 64 one-wave blocks
+void lobk_branch_select(hipStream_t st, const DevParams* Pd, const BranchSrc& a);
 
 // ---- lob_tu_learn.hip ----
 // learn_q_pair_kernel / learn_q_lane_kernel<algo, vt, tr>: vt = 8 when the state has eight variables (else 0)

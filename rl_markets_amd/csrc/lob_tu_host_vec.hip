@@ -1,5 +1,5 @@
 // Host side of the C ABI, the environment's half (include/lob_engine.h; lob_engine_impl.h): lob_step, the vector-env interface
-// lob_vec_* and the book snapshots lob_snapshot_*.  No kernel is compiled here: every launch goes through lob_launch.h (lob_vec_update's
+// lob_vec_*, the branch sets lob_branch_* and the book snapshots lob_snapshot_*.  No kernel is compiled here: every launch goes through lob_launch.h (lob_vec_update's
 // memo refresh through lob_engine.hip's launch_memo).  gfx950 only; no CPU execution path.
 #define LOB_TU_SPLIT 1
 #include "lob_engine_impl.h"
@@ -229,6 +229,109 @@ int lob_vec_rollout(lob_engine* e, const int32_t* dev_actions, int n_plans, int 
         lobk_vec_rollout(e->stream, e->P.T <= 2, (const DevParams*)e->P_dev, e->S, a);
     }
     HIPCHK(hipGetLastError());
+    return LOB_OK;
+}
+
+// ---- branch sets (include/lob_engine.h lob_branch_*; lob_tu_branch.hip; lob_branch.h) ----
+// The set's shape follows from the engine alone: the books, the branches, and the rings of the two PnL windows when the reward reads
+// them (LOB_REWARD_NORMED) -- nothing else ever looks at a branch's ring.
+static BranchSrc branch_src(lob_engine* e, int n_branches, int buf) {
+    const bool win = e->P.reward_measure == LOB_REWARD_NORMED;
+    BranchSrc a;
+    memset(&a, 0, sizeof a);
+    a.set.base = e->branch_buf[buf].p; a.set.lanes = (u64)branch_lanes(e->B, n_branches);
+    a.set.w_up = win ? e->S.pnl_ups.w : 0; a.set.w_dn = win ? e->S.pnl_downs.w : 0;
+    a.from = a.set; a.from.base = e->branch_buf[buf ^ 1].p;
+    a.B = e->B; a.Bpad = (e->B + 63) / 64 * 64;
+    a.n_branches = n_branches;
+    return a;
+}
+// room for a set of n_branches in buffer `buf` (a buffer that must grow is released and allocated: both synchronise the device)
+static int branch_reserve(lob_engine* e, const char* who, int n_branches, int buf) {
+    const BranchSrc a = branch_src(e, n_branches, buf);
+    if (a.set.lanes > (u64)INT32_MAX || e->branch_buf[buf].reserve(branch_bytes(e->B, n_branches, a.set.w_up, a.set.w_dn))) {
+        lob_set_error(branch_enomem_message(who, e->B, n_branches, a.set.w_up, a.set.w_dn));
+        return LOB_ENOMEM;
+    }
+    return LOB_OK;
+}
+static int branch_live_ok(lob_engine* e, const char* who) {
+    if (e->branch_live && e->branch_buf[e->branch_cur].p) return LOB_OK;
+    lob_set_error(std::string(who) + ": no live branch set (lob_branch_fork makes one; lob_reset and lob_branch_close void it)");
+    return LOB_ESTATE;
+}
+
+// Every branch becomes a copy of its book's present state (branch_fork_kernel): one launch on the engine's stream, nothing read back,
+// nothing of the engine's state changed.  Allowed and refused where lob_vec_rollout is.
+int lob_branch_fork(lob_engine* e, int n_branches, const lob_branch_out* out) {
+    if (!e) { lob_set_error("lob_branch_fork: NULL engine"); return LOB_EINVAL; }
+    if (n_branches < 1 || n_branches > LOB_MAX_BRANCHES) {
+        lob_set_error("lob_branch_fork: n_branches = " + std::to_string(n_branches) + " is outside [1, " + std::to_string(LOB_MAX_BRANCHES) + "]"); return LOB_EINVAL;
+    }
+    LOB_GUARD(e, lob_branch_fork);
+    HIPCHK(hipSetDevice(e->device));
+    e->branch_live = false;   // (a growth that fails leaves no set behind)
+    const int rc = branch_reserve(e, "lob_branch_fork", n_branches, e->branch_cur);
+    if (rc) return rc;
+    BranchSrc a = branch_src(e, n_branches, e->branch_cur);
+    if (out) a.out = *out;
+    {
+        TimedLaunch t(e, "branch_fork_kernel", nullptr, true);
+        lobk_branch_fork(e->stream, (const DevParams*)e->P_dev, e->S, a);
+    }
+    HIPCHK(hipGetLastError());
+    e->branch_n = n_branches;
+    e->branch_live = true;
+    return LOB_OK;
+}
+
+// One lob_vec_step of every branch on its private state (branch_step_kernel): one launch on the engine's stream.
+int lob_branch_step(lob_engine* e, const int32_t* dev_actions, const lob_branch_out* out) {
+    if (!e || !out || !dev_actions) { lob_set_error("lob_branch_step: NULL argument"); return LOB_EINVAL; }
+    LOB_GUARD(e, lob_branch_step);
+    int rc = branch_live_ok(e, "lob_branch_step");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    BranchSrc a = branch_src(e, e->branch_n, e->branch_cur);
+    a.index = dev_actions;
+    a.out = *out;
+    {
+        TimedLaunch t(e, "branch_step_kernel", nullptr, true);
+        lobk_branch_step(e->stream, e->P.T <= 2, (const DevParams*)e->P_dev, e->S, a);
+    }
+    HIPCHK(hipGetLastError());
+    return LOB_OK;
+}
+
+// The set rearranged within every book (branch_select_kernel): a gather from the live buffer into the other one, which then is the
+// live one.  One launch on the engine's stream.
+int lob_branch_select(lob_engine* e, const int32_t* dev_parent, const lob_branch_out* out) {
+    if (!e || !dev_parent) { lob_set_error("lob_branch_select: NULL argument"); return LOB_EINVAL; }
+    LOB_GUARD(e, lob_branch_select);
+    int rc = branch_live_ok(e, "lob_branch_select");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    const int to = e->branch_cur ^ 1;
+    if ((rc = branch_reserve(e, "lob_branch_select", e->branch_n, to))) return rc;   // (the live set stays as it is)
+    BranchSrc a = branch_src(e, e->branch_n, to);
+    a.index = dev_parent;
+    if (out) { a.out.obs = out->obs; a.out.terminal = out->terminal; }
+    {
+        TimedLaunch t(e, "branch_select_kernel", nullptr, true);
+        lobk_branch_select(e->stream, (const DevParams*)e->P_dev, a);
+    }
+    HIPCHK(hipGetLastError());
+    e->branch_cur = to;
+    return LOB_OK;
+}
+
+int lob_branch_close(lob_engine* e) {
+    if (!e) { lob_set_error("lob_branch_close: NULL engine"); return LOB_EINVAL; }
+    e->branch_live = false;
+    if (!e->branch_buf[0].p && !e->branch_buf[1].p) return LOB_OK;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));   // (a launch still queued uses the buffers)
+    for (auto& b : e->branch_buf) b.release();
     return LOB_OK;
 }
 

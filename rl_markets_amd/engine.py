@@ -354,6 +354,33 @@ class Engine:
         any before) allocates the engine's workspace, which synchronises the device."""
         self._check(self.lib.lob_vec_rollout(self.h, C.c_void_p(actions_ptr), int(n_plans), int(horizon), float(gamma), C.byref(out)))
 
+    def branch_fork(self, n_branches, out=None):
+        """lob_branch_fork: (re)makes the engine's branch set -- `n_branches` (1 .. abi.MAX_BRANCHES) private copies of every book's
+        present environment state, which stay on the device between calls.  `out` (abi.BranchOut or None: obs f32 [N, B, V], reward
+        f64 [N, B], terminal uint8 [N, B], stepped int32 [N, B]; 0 = not wanted) receives the books' latest observation, their
+        terminal word, reward 0 and stepped 0 in every plane.  Nothing of the engine changes.  Enqueued on the engine's stream; the
+        first fork, and one that needs a larger set than any before, allocates, which synchronises the device.  Refused on a
+        ring-mode stream."""
+        self._check(self.lib.lob_branch_fork(self.h, int(n_branches), None if out is None else C.byref(out)))
+
+    def branch_step(self, actions_ptr, out):
+        """lob_branch_step: one vec_step of every branch on its private state, branch n with the actions int32 [N, B] at the DEVICE
+        address `actions_ptr`; `out` as in branch_fork: bit for bit what vec_step would write had the books been in the branch's
+        state.  A branch that is over does not step (reward 0, its last observation); an action outside 0 .. 8 leaves the branch as
+        it is and is not counted by vec_status.  One launch, enqueued on the engine's stream."""
+        self._check(self.lib.lob_branch_step(self.h, C.c_void_p(actions_ptr), C.byref(out)))
+
+    def branch_select(self, parent_ptr, out=None):
+        """lob_branch_select: branch (n, b) becomes a copy of branch (parent[n, b], b) as it stood before the call (int32 [N, B] at
+        the DEVICE address `parent_ptr`; outside 0 .. N - 1: keeps itself).  `out`: obs and terminal of the new arrangement are
+        written, reward and stepped are not.  One launch; the first select allocates the second buffer, which synchronises the
+        device."""
+        self._check(self.lib.lob_branch_select(self.h, C.c_void_p(parent_ptr), None if out is None else C.byref(out)))
+
+    def branch_close(self):
+        """lob_branch_close: releases the branch set's buffers (waits for the engine's stream); close() does the same."""
+        self._check(self.lib.lob_branch_close(self.h))
+
     def snapshot_save(self, slot, mask_ptr=None):
         """lob_snapshot_save: the environment state of the books selected by the DEVICE mask at address `mask_ptr` (uint8 [B],
         nonzero selects; None: every book, which (re)starts the slot) into snapshot slot `slot` (0 .. abi.MAX_SNAPSHOTS - 1);

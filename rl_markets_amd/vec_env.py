@@ -72,6 +72,39 @@ observation and terminal behind the last, the steps that completed and the disco
 exactly where they are.  An action of -1 skips that step for that book: plans of unequal length.  Not available on a ring-mode
 stream.  A VecEnv that never calls rollout() allocates and launches nothing for it.
 
+branch(n) makes a branch set (lob_branch_fork): n private copies of every book's environment state that stay on the device between
+calls and can be stepped one step at a time with actions a torch policy produces from their observations -- closed loop, where peek()
+and rollout() need every action before the launch.  It returns a Branches object: .obs f32 [n, B, V], .reward f64 [n, B], .terminal
+uint8 [n, B], .stepped int32 [n, B] are persistent tensors (overwritten by the next call: clone what must be kept); .step(actions)
+steps every branch with actions int32 [n, B] (an action outside 0 .. 8 leaves that branch as it is: -1 steps a subset),
+.select(parent) makes branch (i, b) a copy of branch (parent[i, b], b) as it stood, .fork() starts again from the books' present state
+and .close() releases the set.  The books themselves stay exactly where they are and may step on meanwhile; reset() voids the set.
+The return of the engine's own greedy policy over H steps from here:
+
+    br = env.branch(n)
+    ret = torch.zeros((n, B), dtype=torch.float64, device=dev)
+    for h in range(H):
+        a = env.q_values(br.obs.view(n * B, V)).argmax(-1).to(torch.int32).view(n, B)
+        br.step(a)
+        ret += gamma ** h * br.reward
+
+Beam search over quote schedules, k beams per book: one set holds the beams' nine children each, and a round is one select() -- with
+the parents a top-k gives -- and one step():
+
+    br = env.branch(k * 9)
+    child_action = (torch.arange(k * 9, device=dev) % 9).to(torch.int32).unsqueeze(1).expand(k * 9, B).contiguous()
+    beam = torch.zeros((k, B), dtype=torch.int64, device=dev)              # the branches that hold the beams: all alike behind the fork
+    ret = torch.zeros((k, B), dtype=torch.float64, device=dev)
+    for h in range(H):
+        br.select(beam.repeat_interleave(9, dim=0).to(torch.int32))        # branch i: a copy of beam i // 9 ...
+        o, r, t, s = br.step(child_action)                                  # ... under action i % 9
+        total = ret.repeat_interleave(9, dim=0) + gamma ** h * r
+        value = env.q_values(o.view(k * 9 * B, V)).view(k * 9, B, 9).max(-1).values * (t == 0)
+        beam = (total + gamma ** (h + 1) * value).topk(k, dim=0).indices    # the branches the next round descends from
+        ret = total.gather(0, beam)
+
+Not available on a ring-mode stream.  A VecEnv that never calls branch() allocates and launches nothing for it.
+
 step() reads the actions from the tensor's device memory and writes into five persistent tensors (lob_vec_step,
 include/lob_engine.h): no copy to or from the host and no synchronisation.  The engine runs on a stream of its own; it is made
 to wait for torch's current stream before the call (the actions are ready) and torch's current stream for the engine's after it
@@ -245,6 +278,12 @@ class VecEnv:
         self._on_engine(self.eng.vec_rollout, plans.data_ptr(), P, H, gamma, out, inputs=(plans,))
         return obs, reward, terminal, stepped, ret
 
+    def branch(self, n):
+        """lob_branch_fork: the engine's branch set (one per engine) remade as n (1 .. abi.MAX_BRANCHES) copies of every book's
+        present state.  Returns a Branches object (its tensors are allocated here, the engine's buffers by the engine: the first
+        fork, and one that needs more room than any before, synchronises the device)."""
+        return Branches(self, n)
+
     def q_values(self, vars):
         """lob_vec_q: Q(s, .) under the engine's weights (theta; book 0's under private theta) for n free-standing states, f32 [n, V]
         on the engine's device -> a new f64 [n, 9] tensor; bit for bit Engine.q_values of the same rows."""
@@ -339,3 +378,51 @@ class VecEnv:
         is left in .bad_actions).  A malformed event stream raises engine.LobError (LOB_EDATA)."""
         rc, self.bad_actions = self.eng.vec_status()
         return rc
+
+
+class Branches:
+    """A branch set of a VecEnv (VecEnv.branch): n private copies of every book's environment state, stepped and rearranged on the
+    device.  The engine holds one set: making another Branches, or fork() with it, remakes that set."""
+
+    def __init__(self, env, n):
+        if int(n) != n or not 1 <= int(n) <= abi.MAX_BRANCHES:
+            raise ValueError("VecEnv.branch: n must be an integer in 1 .. %d" % abi.MAX_BRANCHES)
+        self.env, self.n = env, int(n)
+        N, B, V, dev = self.n, env.B, env.V, env.device
+        self.obs = torch.zeros((N, B, V), dtype=torch.float32, device=dev)
+        self.reward = torch.zeros((N, B), dtype=torch.float64, device=dev)
+        self.terminal = torch.zeros((N, B), dtype=torch.uint8, device=dev)
+        self.stepped = torch.zeros((N, B), dtype=torch.int32, device=dev)
+        self.out = abi.BranchOut(self.obs.data_ptr(), self.reward.data_ptr(), self.terminal.data_ptr(), self.stepped.data_ptr())
+        self.fork()
+
+    def _words(self, t, who, what):
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or t.device != self.env.device
+                or t.shape != (self.n, self.env.B) or not t.is_contiguous()):
+            raise ValueError("Branches.%s: %s must be a contiguous int32 CUDA tensor of shape (%d, %d) on the engine's device"
+                             % (who, what, self.n, self.env.B))
+
+    def fork(self):
+        """lob_branch_fork again: every branch becomes a copy of its book's present state.  Returns (obs, reward, terminal, stepped):
+        the books' latest observation and terminal word in every plane, reward 0, stepped 0."""
+        self.env._on_engine(self.env.eng.branch_fork, self.n, self.out)
+        return self.obs, self.reward, self.terminal, self.stepped
+
+    def step(self, actions):
+        """lob_branch_step: actions int32 [n, B] on the engine's device.  Returns (obs, reward, terminal, stepped), the persistent
+        tensors: per branch what VecEnv.step would return had the books been in that branch's state."""
+        self._words(actions, "step", "actions")
+        self.env._on_engine(self.env.eng.branch_step, actions.data_ptr(), self.out, inputs=(actions,))
+        return self.obs, self.reward, self.terminal, self.stepped
+
+    def select(self, parent):
+        """lob_branch_select: parent int32 [n, B]; branch (i, b) becomes a copy of branch (parent[i, b], b) as it stood before the
+        call (outside 0 .. n - 1: it keeps itself).  Returns (obs, terminal) of the new arrangement; .reward and .stepped keep the
+        last step's values in the old arrangement."""
+        self._words(parent, "select", "parent")
+        self.env._on_engine(self.env.eng.branch_select, parent.data_ptr(), self.out, inputs=(parent,))
+        return self.obs, self.terminal
+
+    def close(self):
+        """lob_branch_close: releases the engine's buffers of the set (waits for the engine's stream)."""
+        self.env.eng.branch_close()
