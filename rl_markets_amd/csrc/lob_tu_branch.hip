@@ -12,9 +12,7 @@
 
 #include "lob_internal.h"
 #include "lob_kernels.h"
-#include "lob_peek.h"   // the epilogue without its stores: peek_epilogue_apply, peek_reward
-
-#define LOB_BRANCH_BLOCK 64   // one wave per block: 64 consecutive books of one branch (vec_peek_kernel's shape)
+#include "lob_peek.h"   // the family's shape and its private step
 
 static constexpr BranchOff BR_OFF = branch_off();
 
@@ -45,27 +43,14 @@ __device__ inline RMPtrs br_window(const BranchSet& s, int which, i32 w) {
 }
 __device__ __forceinline__ float4* br_obs(const BranchSet& s, size_t lane) { return reinterpret_cast<float4*>(br_arr<f32>(s, BR_OFF.obs) + lane * 16); }
 
-__device__ __forceinline__ int br_terminal(const DevParams& P, i32 done, i32 time_ms) {   // lob_get_terminal (lob_tu_vec.hip vec_terminal)
-    return done == 2 ? 2 : (is_open(P, time_ms) ? 0 : 1);
-}
-
-// The block's staged rows ([64][V] in LDS) leave as consecutive words: they are contiguous in the branch's plane (vec_rows_out,
-// lob_tu_vec.hip).  Every thread of the block calls this (block barrier).
-__device__ __forceinline__ void br_rows_out(const f32* stage, f32* obs, int n, int B, int first_b, int V) {
-    __syncthreads();
-    const int rows = B - first_b < LOB_BRANCH_BLOCK ? B - first_b : LOB_BRANCH_BLOCK;
-    f32* dst = obs + ((size_t)n * (size_t)B + (size_t)first_b) * (size_t)V;
-    for (int i = threadIdx.x; i < rows * V; i += LOB_BRANCH_BLOCK) dst[i] = stage[i];
-}
-
 // lob_branch_fork: one lane per book reads the book's present state once -- the LOB_ENV_FIELDS, the running state of the two windows,
 // slot 2 of S.vars -- and writes it to the N lanes of the book, consecutive books to consecutive words on both sides; then the rings,
 // entry by entry, when the set holds them.  Every load of a group is issued before its first store.  out (members may be null):
 // plane n = the observation, lob_get_terminal's value, reward +0.0, stepped 0.
-__global__ void __launch_bounds__(LOB_BRANCH_BLOCK) branch_fork_kernel(const DevParams* __restrict__ Pp, DevState S, BranchSrc a) {
+__global__ void __launch_bounds__(LOB_LOOK_BLOCK) branch_fork_kernel(const DevParams* __restrict__ Pp, DevState S, BranchSrc a) {
     const DevParams& P = *Pp;
-    __shared__ f32 stage[LOB_BRANCH_BLOCK * LOB_MAX_VARS];
-    const int first_b = blockIdx.x * LOB_BRANCH_BLOCK;
+    __shared__ f32 stage[LOB_LOOK_BLOCK * LOB_MAX_VARS];
+    const int first_b = blockIdx.x * LOB_LOOK_BLOCK;
     const int b = first_b + threadIdx.x;
     const int B = a.B, V = P.V, N = a.n_branches;
     const BranchSet& set = a.set;
@@ -93,7 +78,7 @@ __global__ void __launch_bounds__(LOB_BRANCH_BLOCK) branch_fork_kernel(const Dev
             const f64 x = S.pnl_downs.ring[(size_t)k * B + b];
             for (int n = 0; n < N; n++) rd.ring[(size_t)k * set.lanes + (size_t)n * (size_t)a.Bpad + (size_t)b] = x;
         }
-        const uint8_t term = (uint8_t)br_terminal(P, e.done, e.time_ms);
+        const uint8_t term = (uint8_t)lob_terminal(P, e.done, e.time_ms);
         for (int n = 0; n < N; n++) {
             const size_t o = (size_t)n * (size_t)B + (size_t)b;
             if (out.reward) out.reward[o] = 0.0;
@@ -107,27 +92,18 @@ __global__ void __launch_bounds__(LOB_BRANCH_BLOCK) branch_fork_kernel(const Dev
                 if (i < V) stage[threadIdx.x * V + i] = v[i];
         }
     }
-    if (out.obs) {   // (uniform)
-        __syncthreads();
-        const int rows = B - first_b < LOB_BRANCH_BLOCK ? B - first_b : LOB_BRANCH_BLOCK;
-        for (int n = 0; n < N; n++) {
-            f32* dst = out.obs + ((size_t)n * (size_t)B + (size_t)first_b) * (size_t)V;
-            for (int i = threadIdx.x; i < rows * V; i += LOB_BRANCH_BLOCK) dst[i] = stage[i];
-        }
-    }
+    if (out.obs) look_rows_out(stage, out.obs, 0, N, B, first_b, V);   // (uniform)
 }
 
 // lob_branch_select: one lane per (child, book), branch-major.  Child (n, b) becomes a copy of branch (parent[n][b], b) of the OTHER
 // buffer `a.from` -- the set as it stood before the call --, a parent outside [0, N) meaning itself; the host swaps the buffers' roles.
 // A gather between lanes of the same book: the loads of a wave are coalesced when its books share a parent, its stores always.  All
 // loads of a group before its first store.  out (members may be null): obs and terminal of the new arrangement.
-__global__ void __launch_bounds__(LOB_BRANCH_BLOCK) branch_select_kernel(const DevParams* __restrict__ Pp, BranchSrc a) {
+__global__ void __launch_bounds__(LOB_LOOK_BLOCK) branch_select_kernel(const DevParams* __restrict__ Pp, BranchSrc a) {
     const DevParams& P = *Pp;
-    __shared__ f32 stage[LOB_BRANCH_BLOCK * LOB_MAX_VARS];
-    const int per_plane = a.Bpad / LOB_BRANCH_BLOCK;
-    const int n = blockIdx.x / per_plane;
-    const int first_b = (blockIdx.x - n * per_plane) * LOB_BRANCH_BLOCK;
-    const int b = first_b + threadIdx.x;
+    __shared__ f32 stage[LOB_LOOK_BLOCK * LOB_MAX_VARS];
+    const LookPlane pl = look_plane(a.Bpad);
+    const int n = pl.plane, b = pl.b;
     const int B = a.B, V = P.V;
     const BranchSet &dst = a.set, &src = a.from;
     const lob_branch_out& out = a.out;
@@ -154,7 +130,7 @@ __global__ void __launch_bounds__(LOB_BRANCH_BLOCK) branch_select_kernel(const D
         }
         for (int k = w_min; k < src.w_up; k++) du.ring[(size_t)k * dst.lanes + to] = su.ring[(size_t)k * src.lanes + from];
         for (int k = w_min; k < src.w_dn; k++) dd.ring[(size_t)k * dst.lanes + to] = sd.ring[(size_t)k * src.lanes + from];
-        if (out.terminal) out.terminal[(size_t)n * (size_t)B + (size_t)b] = (uint8_t)br_terminal(P, e.done, e.time_ms);
+        if (out.terminal) out.terminal[(size_t)n * (size_t)B + (size_t)b] = (uint8_t)lob_terminal(P, e.done, e.time_ms);
         if (out.obs) {
             const f32 v[16] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y, v2.z, v2.w, v3.x, v3.y, v3.z, v3.w};
 #pragma unroll
@@ -162,30 +138,28 @@ __global__ void __launch_bounds__(LOB_BRANCH_BLOCK) branch_select_kernel(const D
                 if (i < V) stage[threadIdx.x * V + i] = v[i];
         }
     }
-    if (out.obs) br_rows_out(stage, out.obs, n, B, first_b, V);   // (uniform)
+    if (out.obs) look_rows_out(stage, out.obs, n, 1, B, pl.first_b, V);   // (uniform)
 }
 
 // lob_branch_step: one lane per (branch, book), branch-major: block i is branch i / blocks_per_plane over the books
 // 64 * (i % blocks_per_plane) ..., so every load and store of the set and actions[n * B + b] are consecutive words across the wave.
-// The step is vec_rollout_kernel's loop body (lob_tu_vecroll.hip), call for call, between a load and a store of the lane's state:
-// lob_vec_step's rules on the private state -- a branch steps when its lob_get_terminal is 0 and its action is one of the nine;
+// The step up to the event loop's status is the family's (lob_peek.h look_step_loads / look_step_run), as in vec_rollout_kernel's
+// loop, between a load and a store of the lane's state; what follows a completed step is written out below.  lob_vec_step's rules on the private state -- a branch steps when its lob_get_terminal is 0 and its action is one of the nine;
 // otherwise, and when the step runs dry (the mutated state is kept, done == 2), the reward is +0.0 and the observation stays that of
 // the last completed step.  The lane owns a full ring of each window when the reward reads them, so the plain rm_prep (lob_env.h)
 // finds the entry a full window replaces, the lane's own pushes included.  Under every other reward nothing reads the windows: they
-// stay as forked.  The state goes back only on lanes that stepped or ran dry; the epilogue is lob_peek.h's, over registers, so no
-// store reaches the engine's windows.  EnvCtx keeps the real S and b: the track, the records, the meta.
+// stay as forked.  The state goes back only on lanes that stepped or ran dry; the epilogue runs over registers, so no store reaches
+// the engine's windows.  EnvCtx keeps the real S and b: the track, the records, the meta.
 template <bool T2>
-__global__ void __launch_bounds__(LOB_BRANCH_BLOCK) branch_step_kernel(const DevParams* __restrict__ Pp, DevState S, BranchSrc a) {
+__global__ void __launch_bounds__(LOB_LOOK_BLOCK) branch_step_kernel(const DevParams* __restrict__ Pp, DevState S, BranchSrc a) {
     const DevParams& P = *Pp;  // parameters read through the scalar cache, never copied to scratch
     constexpr int TM = T2 ? 2 : LOB_MAX_TRADES;
     __shared__ TickLds tick_lds;
     stage_ticks(P, tick_lds);
-    __shared__ EnvSlot lds_env[LOB_BRANCH_BLOCK];
-    __shared__ f32 stage[LOB_BRANCH_BLOCK * LOB_MAX_VARS];
-    const int per_plane = a.Bpad / LOB_BRANCH_BLOCK;
-    const int n = blockIdx.x / per_plane;
-    const int first_b = (blockIdx.x - n * per_plane) * LOB_BRANCH_BLOCK;
-    const int b = first_b + threadIdx.x;
+    __shared__ EnvSlot lds_env[LOB_LOOK_BLOCK];
+    __shared__ f32 stage[LOB_LOOK_BLOCK * LOB_MAX_VARS];
+    const LookPlane pl = look_plane(a.Bpad);
+    const int n = pl.plane, b = pl.b;
     const int B = a.B, V = P.V;
     const BranchSet& set = a.set;
     const lob_branch_out& out = a.out;
@@ -199,48 +173,30 @@ __global__ void __launch_bounds__(LOB_BRANCH_BLOCK) branch_step_kernel(const Dev
         f64 reward = 0.0;
         int stepped = 0;
         bool have_obs = false;
-        const int term = br_terminal(P, e.done, e.time_ms);
+        const int term = lob_terminal(P, e.done, e.time_ms);
         if (term == 0 && action >= 0 && action < LOB_N_ACTIONS) {
             const bool win = P.reward_measure == LOB_REWARD_NORMED;   // (the set holds the rings exactly then: lob_branch_fork)
             const RMPtrs ru = br_window(set, 0, S.pnl_ups.w), rd = br_window(set, 1, S.pnl_downs.w);
-            RMReg wu, wd;
-            wu.cnt = wu.head = wu.slot = 0; wu.sum = wu.mean = wu.s = wu.old = 0.0;
-            wd = wu;
+            RMReg wu = rm_zero(), wd = wu;
             if (win) { rm_load(ru, (int)lane, wu); rm_load(rd, (int)lane, wd); }
-            // what the step's launch reads back of the previous one's env_store: the cursor's track entry, its row, the next row
-            const int rc0 = e.rec_cur;
-            const TrackHead64 t0 = c.track_head64(e.k);
-            RowFull cur;
-            row_full_load(c, rc0, cur);
-            RowFull first;
-            if (LOB_FAST_PASS && TM == 2) { const int last_row = c.n_ev() - 1; row_full_load(c, rc0 + 1 < last_row ? rc0 + 1 : last_row, first); }
+            LookLoads L;
+            look_step_loads<TM>(c, e.k, e.rec_cur, L);
             StepAgg g;
-            step_prologue(c, e, action, g, cur);
-            int st;
-            if (LOB_FAST_PASS && TM == 2) {
-                TrackHead64 t = t0;
-                st = event_loop_fast(c, e, g, t, first);
-            } else {
-                TrackHead t;
-                t.rec_first = t0.rec_first; t.rec_last = t0.rec_last; t.time_ms = t0.time_ms; t.tick_ap0 = t0.tick_ap0;
-                t.tick_bp0 = t0.tick_bp0; t.info = t0.info; t.mid = t0.mid;
-                do {
-                    const TrackHead tn = c.track_head(e.k + 1);
-                    st = step_event<TM>(c, e, g, t);
-                    t = tn;
-                } while (st == 0);
-            }
+            const int st = look_step_run<TM>(c, e, action, g, L);
             if (st != 2) {
+                // What follows is written out here and not through look_step_finish: with it this kernel measured 0.4 % slower than
+                // before the step was shared.  The push and the episode totals stand in BOTH arms on purpose: written once behind the
+                // `if`, the compiler spills 33 SGPRs for two trade slots against 31 (without the rings nothing reads the windows).
                 e.pnl_step = g.pnl;
                 if (win) {
                     rm_prep(ru, (int)set.lanes, (int)lane, wu); rm_prep(rd, (int)set.lanes, (int)lane, wd);
                     const int slot_u = wu.slot, slot_d = wd.slot;
-                    peek_epilogue_apply(c, e, g, wu, wd);
+                    peek_push(c, e, wu, wd); e.ep_reward += g.r; e.ep_bandh += g.mpm;
                     ru.ring[(size_t)slot_u * set.lanes + lane] = peek_push_up(e);    // rm_apply's two stores: the ring slot ...
                     rd.ring[(size_t)slot_d * set.lanes + lane] = peek_push_down(e);
                     rm_store(ru, (int)lane, wu); rm_store(rd, (int)lane, wd);        // ... and the running state
                 } else {
-                    peek_epilogue_apply(c, e, g, wu, wd);
+                    peek_push(c, e, wu, wd); e.ep_reward += g.r; e.ep_bandh += g.mpm;
                 }
                 const Track tk = state_track(c, e);
                 for (int i = 0; i < V; i++) stage[threadIdx.x * V + i] = (f32)get_variable(c, e, P.vars[i], tk);
@@ -262,20 +218,20 @@ __global__ void __launch_bounds__(LOB_BRANCH_BLOCK) branch_step_kernel(const Dev
             for (int i = 0; i < V; i++) stage[threadIdx.x * V + i] = vf[i];
         }
         if (out.reward) out.reward[o] = reward;
-        if (out.terminal) out.terminal[o] = (uint8_t)br_terminal(P, e.done, e.time_ms);
+        if (out.terminal) out.terminal[o] = (uint8_t)lob_terminal(P, e.done, e.time_ms);
         if (out.stepped) out.stepped[o] = stepped;
     }
-    if (out.obs) br_rows_out(stage, out.obs, n, B, first_b, V);   // (uniform)
+    if (out.obs) look_rows_out(stage, out.obs, n, 1, B, pl.first_b, V);   // (uniform)
 }
 
 void lobk_branch_fork(hipStream_t st, const DevParams* Pd, const DevState& S, const BranchSrc& a) {
-    hipLaunchKernelGGL(branch_fork_kernel, dim3((unsigned)(a.Bpad / LOB_BRANCH_BLOCK)), dim3(LOB_BRANCH_BLOCK), 0, st, Pd, S, a);
+    hipLaunchKernelGGL(branch_fork_kernel, dim3((unsigned)(a.Bpad / LOB_LOOK_BLOCK)), dim3(LOB_LOOK_BLOCK), 0, st, Pd, S, a);
 }
 void lobk_branch_select(hipStream_t st, const DevParams* Pd, const BranchSrc& a) {
-    hipLaunchKernelGGL(branch_select_kernel, dim3((unsigned)(a.n_branches * (a.Bpad / LOB_BRANCH_BLOCK))), dim3(LOB_BRANCH_BLOCK), 0, st, Pd, a);
+    hipLaunchKernelGGL(branch_select_kernel, dim3((unsigned)(a.n_branches * (a.Bpad / LOB_LOOK_BLOCK))), dim3(LOB_LOOK_BLOCK), 0, st, Pd, a);
 }
 void lobk_branch_step(hipStream_t st, bool t2, const DevParams* Pd, const DevState& S, const BranchSrc& a) {
-    const dim3 grid((unsigned)(a.n_branches * (a.Bpad / LOB_BRANCH_BLOCK))), block(LOB_BRANCH_BLOCK);
+    const dim3 grid((unsigned)(a.n_branches * (a.Bpad / LOB_LOOK_BLOCK))), block(LOB_LOOK_BLOCK);
     if (t2) hipLaunchKernelGGL(branch_step_kernel<true>, grid, block, 0, st, Pd, S, a);
     else hipLaunchKernelGGL(branch_step_kernel<false>, grid, block, 0, st, Pd, S, a);
 }

@@ -5,17 +5,15 @@
 // to device memory -- and nothing of the engine's state moves.  It is vec_peek_kernel (lob_tu_vecpeek.hip) with a loop around the step:
 // the agent half runs on a private copy of the book's scalars (EnvR in an LDS slot, env_load once) that carries from step to step
 // exactly what env_store would have written and the next launch's env_load read back; the market half is the track the pre-pass has
-// written, followed through the private cursor e.k / e.rec_cur.  The epilogue is lob_peek.h's, without stores.  What one step did not
-// need: the entry a full PnL window replaces may be one the plan itself has pushed (roll_rm_prep below).
+// written, followed through the private cursor e.k / e.rec_cur.  The step is the family's one private step (lob_peek.h).  What one
+// step did not need: the entry a full PnL window replaces may be one the plan itself has pushed (roll_rm_prep below).
 #define LOB_TU_SPLIT 1
 #define LOB_TU_VECROLL 1
 #include <hip/hip_runtime.h>
 
 #include "lob_internal.h"
 #include "lob_kernels.h"
-#include "lob_peek.h"
-
-#define LOB_ROLL_BLOCK 64   // one wave per block: 64 consecutive books under one plan (vec_peek_kernel's shape)
+#include "lob_peek.h"   // the family's shape and its private step
 
 // rm_prep (lob_env.h) `n` pushes into a look-ahead that stores nothing.  A window of w entries that is full replaces the entry w pushes
 // back: the n-th push of the look-ahead (n = 0, 1, ...) meets one of its own if and only if n >= w, whatever the fill at entry --
@@ -43,17 +41,15 @@ __device__ inline void roll_rm_prep(const RMPtrs& r, int B, int b, RMReg& g, int
 // out of range are compared, never used, and not counted.
 //   The rows leave through LDS as in vec_rows_out (lob_tu_vec.hip): the block's rows are contiguous in the plan's plane.
 template <bool T2>
-__global__ void __launch_bounds__(LOB_ROLL_BLOCK) vec_rollout_kernel(const DevParams* __restrict__ Pp, DevState S, RolloutSrc a) {
+__global__ void __launch_bounds__(LOB_LOOK_BLOCK) vec_rollout_kernel(const DevParams* __restrict__ Pp, DevState S, RolloutSrc a) {
     const DevParams& P = *Pp;  // parameters read through the scalar cache, never copied to scratch
     constexpr int TM = T2 ? 2 : LOB_MAX_TRADES;
     __shared__ TickLds tick_lds;
     stage_ticks(P, tick_lds);
-    __shared__ EnvSlot lds_env[LOB_ROLL_BLOCK];
-    __shared__ f32 stage[LOB_ROLL_BLOCK * LOB_MAX_VARS];
-    const int per_plane = a.Bpad / LOB_ROLL_BLOCK;
-    const int p = blockIdx.x / per_plane;
-    const int first_b = (blockIdx.x - p * per_plane) * LOB_ROLL_BLOCK;
-    const int b = first_b + threadIdx.x;
+    __shared__ EnvSlot lds_env[LOB_LOOK_BLOCK];
+    __shared__ f32 stage[LOB_LOOK_BLOCK * LOB_MAX_VARS];
+    const LookPlane pl = look_plane(a.Bpad);
+    const int p = pl.plane, b = pl.b;
     const int B = a.B, V = P.V, H = a.horizon;
     const lob_vec_rollout_out& out = a.out;
     if (b < B) {
@@ -62,50 +58,25 @@ __global__ void __launch_bounds__(LOB_ROLL_BLOCK) vec_rollout_kernel(const DevPa
         env_load(S, b, e);
         // the two PnL windows: read by the LOB_REWARD_NORMED reward only, so only kept then
         const bool win = P.reward_measure == LOB_REWARD_NORMED;
-        RMReg wu, wd;
-        wu.cnt = wu.head = wu.slot = 0; wu.sum = wu.mean = wu.s = wu.old = 0.0;
-        wd = wu;
+        RMReg wu = rm_zero(), wd = wu;
         if (win) { rm_load(S.pnl_ups, b, wu); rm_load(S.pnl_downs, b, wd); }
         const size_t lanes = (size_t)a.n_plans * (size_t)a.Bpad, lane = (size_t)p * (size_t)a.Bpad + (size_t)b;
         f64* const sh_u = a.shadow;
         f64* const sh_d = a.shadow ? a.shadow + (size_t)S.pnl_ups.w * lanes : nullptr;
         f64 prev_u = 0.0, prev_d = 0.0;
-        if (out.obs) {
-            const f32* vf = S.vars + ((size_t)b * 3 + 2) * 16;
-            for (int i = 0; i < V; i++) stage[threadIdx.x * V + i] = vf[i];
-        }
+        if (out.obs) look_obs_slot2(S, b, &stage[threadIdx.x * V], V);
         int n_done = 0;
         f64 acc = 0.0, disc = 1.0;
         const i32* act = a.actions + (size_t)p * (size_t)H * (size_t)B + (size_t)b;
         for (int h = 0; h < H; h++) {
             const int action = act[(size_t)h * (size_t)B];
             f64 reward = 0.0;
-            const int term = e.done == 2 ? 2 : (is_open(P, e.time_ms) ? 0 : 1);   // lob_get_terminal (lob_tu_vec.hip vec_terminal)
-            if (term == 0 && action >= 0 && action < LOB_N_ACTIONS) {
-                // what the step's launch reads back of the previous one's env_store: the cursor's track entry, its row, the next row
-                const int rc0 = e.rec_cur;
-                const TrackHead64 t0 = c.track_head64(e.k);
-                RowFull cur;
-                row_full_load(c, rc0, cur);
-                RowFull first;
-                if (LOB_FAST_PASS && TM == 2) { const int last_row = c.n_ev() - 1; row_full_load(c, rc0 + 1 < last_row ? rc0 + 1 : last_row, first); }
+            if (lob_terminal(P, e.done, e.time_ms) == 0 && action >= 0 && action < LOB_N_ACTIONS) {
+                // the private cursor stands where the previous step's env_store would have left the engine's
+                LookLoads L;
+                look_step_loads<TM>(c, e.k, e.rec_cur, L);
                 StepAgg g;
-                step_prologue(c, e, action, g, cur);
-                int st;
-                if (LOB_FAST_PASS && TM == 2) {
-                    TrackHead64 t = t0;
-                    st = event_loop_fast(c, e, g, t, first);
-                } else {
-                    TrackHead t;
-                    t.rec_first = t0.rec_first; t.rec_last = t0.rec_last; t.time_ms = t0.time_ms; t.tick_ap0 = t0.tick_ap0;
-                    t.tick_bp0 = t0.tick_bp0; t.info = t0.info; t.mid = t0.mid;
-                    do {
-                        const TrackHead tn = c.track_head(e.k + 1);
-                        st = step_event<TM>(c, e, g, t);
-                        t = tn;
-                    } while (st == 0);
-                }
-                if (st != 2) {
+                if (look_step_run<TM>(c, e, action, g, L) != 2) {
                     e.pnl_step = g.pnl;
                     if (win) {
                         roll_rm_prep(S.pnl_ups, S.B, b, wu, n_done, prev_u, sh_u, lanes, lane);
@@ -116,12 +87,8 @@ __global__ void __launch_bounds__(LOB_ROLL_BLOCK) vec_rollout_kernel(const DevPa
                             sh_d[(size_t)(n_done % S.pnl_downs.w) * lanes + lane] = prev_d;
                         }
                     }
-                    peek_epilogue_apply(c, e, g, wu, wd);
-                    if (out.obs) {
-                        const Track tk = state_track(c, e);
-                        for (int i = 0; i < V; i++) stage[threadIdx.x * V + i] = (f32)get_variable(c, e, P.vars[i], tk);
-                    }
-                    reward = peek_reward(c, e, wu, wd);
+                    peek_push(c, e, wu, wd);
+                    reward = look_step_finish(c, e, g, wu, wd, out.obs != nullptr, stage, V);
                     n_done++;
                 }
             }
@@ -130,20 +97,15 @@ __global__ void __launch_bounds__(LOB_ROLL_BLOCK) vec_rollout_kernel(const DevPa
             disc = __dmul_rn(disc, a.gamma);
         }
         const size_t o = (size_t)p * (size_t)B + (size_t)b;
-        if (out.terminal) out.terminal[o] = (uint8_t)(e.done == 2 ? 2 : (is_open(P, e.time_ms) ? 0 : 1));
+        if (out.terminal) out.terminal[o] = (uint8_t)lob_terminal(P, e.done, e.time_ms);
         if (out.stepped) out.stepped[o] = n_done;
         if (out.ret) out.ret[o] = acc;
     }
-    if (out.obs) {   // (uniform)
-        __syncthreads();
-        const int rows = B - first_b < LOB_ROLL_BLOCK ? B - first_b : LOB_ROLL_BLOCK;
-        f32* dst = out.obs + ((size_t)p * (size_t)B + (size_t)first_b) * (size_t)V;
-        for (int i = threadIdx.x; i < rows * V; i += LOB_ROLL_BLOCK) dst[i] = stage[i];
-    }
+    if (out.obs) look_rows_out(stage, out.obs, p, 1, B, pl.first_b, V);   // (uniform)
 }
 
 void lobk_vec_rollout(hipStream_t st, bool t2, const DevParams* Pd, const DevState& S, const RolloutSrc& a) {
-    const dim3 grid((unsigned)(a.n_plans * (a.Bpad / LOB_ROLL_BLOCK))), block(LOB_ROLL_BLOCK);
+    const dim3 grid((unsigned)(a.n_plans * (a.Bpad / LOB_LOOK_BLOCK))), block(LOB_LOOK_BLOCK);
     if (t2) hipLaunchKernelGGL(vec_rollout_kernel<true>, grid, block, 0, st, Pd, S, a);
     else hipLaunchKernelGGL(vec_rollout_kernel<false>, grid, block, 0, st, Pd, S, a);
 }

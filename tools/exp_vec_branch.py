@@ -11,7 +11,7 @@ random steps into the episode; every timed window starts from a fresh fork of th
      clones and the policy --, against fork() + four (policy, Branches.step()) rounds; host clock around one route plus one synchronise.
 All legs are taken in turn, once per round, in this one process; median, min and max over `--rounds` rounds (after `--warm` untimed
 ones).  Before the rounds the outputs of the two closed-loop routes are compared for equality.
-    python tools/exp_vec_branch.py [books ...] [--rounds 21] [--warm 3] [--calls 5] [--mid 30] [--out profiles/vec_branch.json]"""
+    python tools/exp_vec_branch.py [books ...] [--rounds 21] [--warm 3] [--calls 5] [--mid 30] [--trades 2] [--out profiles/vec_branch.json]"""
 import json
 import os
 import sys
@@ -36,8 +36,9 @@ def take(flag, default=None, cast=str):
 
 out_path = take("--out")
 ROUNDS, WARM, CALLS, MID = take("--rounds", 21, int), take("--warm", 3, int), take("--calls", 5, int), take("--mid", 30, int)
+TRADES = take("--trades", 2, int)   # 2: the kernels of two trade slots (<true>); 3: the general ones (<false>)
 BATCHES = [int(x) for x in sys.argv[1:]] or [65536, 4096]
-DEPTH, TRADES, NA = 10, 2, abi.LOB_N_ACTIONS
+DEPTH, NA = 10, abi.LOB_N_ACTIONS
 SIZES = [1, 9, 32]
 ROUTE = (9, 4)
 BYTES_PER_LANE = 416   # lob_branch.h: 288 of LOB_ENV_FIELDS + 2 x 32 of the windows' running state + 64 of the observation (no rings: PnL reward)

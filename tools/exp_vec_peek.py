@@ -8,7 +8,7 @@ the same books) --
   d  env.step() under a torch policy with and without a peek() in front: host clock around `--steps` steps plus one synchronise.
 All legs are taken in turn, once per round, in this one process; median, min and max over `--rounds` rounds (after `--warm` untimed
 ones).  Before the rounds the nine planes of peek() are compared with the route's clones for equality.
-    python tools/exp_vec_peek.py [books ...] [--rounds 21] [--warm 3] [--steps 20] [--calls 5] [--mid 30] [--out profiles/vec_peek.json]"""
+    python tools/exp_vec_peek.py [books ...] [--rounds 21] [--warm 3] [--steps 20] [--calls 5] [--mid 30] [--trades 2] [--out profiles/vec_peek.json]"""
 import json
 import os
 import sys
@@ -33,8 +33,9 @@ def take(flag, default=None, cast=str):
 
 out_path = take("--out")
 ROUNDS, WARM, STEPS, CALLS, MID = take("--rounds", 21, int), take("--warm", 3, int), take("--steps", 20, int), take("--calls", 5, int), take("--mid", 30, int)
+TRADES = take("--trades", 2, int)   # 2: the kernels of two trade slots (<true>); 3: the general ones (<false>)
 BATCHES = [int(x) for x in sys.argv[1:]] or [65536, 4096]
-DEPTH, TRADES, N, ONE = 10, 2, abi.LOB_N_ACTIONS, 4
+DEPTH, N, ONE = 10, abi.LOB_N_ACTIONS, 4
 
 
 def policy_torch(obs):

@@ -9,7 +9,7 @@ starts from the same books) --
      synchronise.
 All legs are taken in turn, once per round, in this one process; median, min and max over `--rounds` rounds (after `--warm` untimed
 ones).  Before the rounds the outputs of rollout(9, 4) are compared with the route's clones for equality.
-    python tools/exp_vec_rollout.py [books ...] [--rounds 21] [--warm 3] [--calls 5] [--mid 30] [--out profiles/vec_rollout.json]"""
+    python tools/exp_vec_rollout.py [books ...] [--rounds 21] [--warm 3] [--calls 5] [--mid 30] [--trades 2] [--out profiles/vec_rollout.json]"""
 import json
 import os
 import sys
@@ -34,8 +34,9 @@ def take(flag, default=None, cast=str):
 
 out_path = take("--out")
 ROUNDS, WARM, CALLS, MID = take("--rounds", 21, int), take("--warm", 3, int), take("--calls", 5, int), take("--mid", 30, int)
+TRADES = take("--trades", 2, int)   # 2: the kernels of two trade slots (<true>); 3: the general ones (<false>)
 BATCHES = [int(x) for x in sys.argv[1:]] or [65536, 4096]
-DEPTH, TRADES, N, GAMMA = 10, 2, abi.LOB_N_ACTIONS, 0.97
+DEPTH, N, GAMMA = 10, abi.LOB_N_ACTIONS, 0.97
 SHAPES = [(9, 1), (9, 4), (9, 8), (32, 8)]
 ROUTE = (9, 4)
 
