@@ -789,7 +789,9 @@ int lob_td_step_end(lob_engine* e);
  * caller that cannot split runs the whole step and exchanges after it -- asked for explicitly instead of being inferred
  * from a LOB_ESTATE of lob_td_step_begin, which has other causes (no reset, a half step left open). */
 int lob_td_split_supported(lob_engine* e);
-/* Backtester::_step (serial.cpp:124-137): greedy action, no learning. */
+/* Backtester::_step (serial.cpp:124-137): greedy action, no learning.  The reference's Backtester is a runner of its own; here a
+ * greedy step may stand among learner steps, and like lob_step and lob_vec_step it leaves the state BEHIND the step in the learner's
+ * `state` object: the lob_td_step that follows chooses its action in the books' present state. */
 int lob_eval_step(lob_engine* e, int32_t n_steps);
 /* Agent::HandleTerminal (src/rl/agent.cpp:103-109): traces.decay(0). The
  * alpha / epsilon schedules are evaluated by the host adaptor. */

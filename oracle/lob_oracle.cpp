@@ -121,6 +121,13 @@ template <class C> struct Book {
     long observed_transaction_volume_ = 0;
 
     explicit Book(int depth) : D(depth), prices(depth, 0.0), last_prices(depth, 0.0) {}
+    // a deep copy (oracle_copy_books): the orders are owned, so each one is made again
+    Book(const Book& o)
+        : D(o.D), cmp(o.cmp), prices(o.prices), last_prices(o.last_prices), levels(o.levels), last_levels(o.last_levels),
+          total_volume_(o.total_volume_), last_total_volume_(o.last_total_volume_), n_transacted_(o.n_transacted_),
+          observed_transaction_value_(o.observed_transaction_value_), observed_transaction_volume_(o.observed_transaction_volume_) {
+        for (const auto& kv : o.open_orders) open_orders.emplace(kv.first, std::unique_ptr<Order>(new Order(*kv.second)));
+    }
 
     void Reset() {  // book.cpp:144-160
         n_transacted_ = 0;
@@ -1460,24 +1467,66 @@ int oracle_eval_step(oracle_learner* o, int32_t n_steps) {  // Backtester::_step
             if (e.isTerminal()) { o->done[b] = 1; continue; }
             o->new_state(b);
             int a = o->action(b, o->feats[b], true);
-            if (!e.performAction(a)) { o->done[b] = 2; e.fill(o->recs[b].book); continue; }
+            if (!e.performAction(a)) {   // (the record keeps what the learner's own dry step records: the draws made, the traces)
+                o->done[b] = 2; o->recs[b].rng_ctr = o->rng_ctr[b]; e.fill(o->recs[b].book); o->recs[b].book.n_traces = (int)o->traces[b].nonzero.size(); continue;
+            }
             o->n_steps_done++;
-            o->record(b, a, e.getReward(), 0.0);
+            o->record(b, a, e.getReward(), 0.0);   // (the state the action was chosen in: the Backtester's order)
+            // The Backtester is a runner of its own in the reference, with State objects of its own; nothing there says what a
+            // Learner::_step finds behind it.  The engine writes the state behind EVERY completed step -- learner, greedy or
+            // lob_step / lob_vec_step -- to the learner's `state` object, so a learner step behind a greedy one acts on the present
+            // state (include/lob_engine.h lob_eval_step); the oracle does the same, behind the record.
+            o->new_state(b);
         }
     return 0;
 }
 
 int oracle_env_step(oracle_learner* o, const int32_t* actions) {
     for (int b = 0; b < o->B; b++) {
+        if (actions[b] < 0 || actions[b] >= LOB_N_ACTIONS) continue;  // lob_vec_step's rule: the book is not stepped in this call
         if (o->done[b]) continue;
         Env& e = *o->env[b];
         if (e.isTerminal()) { o->done[b] = 1; continue; }
-        if (!e.performAction(actions[b])) { o->done[b] = 2; e.fill(o->recs[b].book); continue; }
+        if (!e.performAction(actions[b])) { o->done[b] = 2; e.fill(o->recs[b].book); o->recs[b].book.n_traces = (int)o->traces[b].nonzero.size(); continue; }
         o->new_state(b);
         o->n_steps_done++;
         o->record(b, actions[b], e.getReward(), 0.0);
     }
     return 0;
+}
+
+// The environment side of book src_idx[i] of `src` becomes that of book dst_idx[i] of `dst` (the two may be one oracle; the copies
+// are made in order): the environment itself, the runner's done flag and the last record (with the state vector in it) --
+// what lob_snapshot_restore puts back and what a branch set holds.  The learner of the target book stays: weights, traces, random
+// counter.  Both oracles must have been created with the same environment parameters.  tests/test_vec_model.py: a copy continues
+// bit for bit like a replay.
+int oracle_copy_books(oracle_learner* dst, const int32_t* dst_idx, oracle_learner* src, const int32_t* src_idx, int32_t n) {
+    for (int i = 0; i < n; i++)
+        if (dst_idx[i] < 0 || dst_idx[i] >= dst->B || src_idx[i] < 0 || src_idx[i] >= src->B) return -1;
+    for (int i = 0; i < n; i++) {
+        const int d = dst_idx[i], s = src_idx[i];
+        if (dst == src && d == s) continue;
+        dst->env[d].reset(new Env(*src->env[s]));
+        dst->done[d] = src->done[s];
+        // (not vars / feats: they are the learner's `state` object, which lob_snapshot_restore leaves as it is -- the first learner
+        // step behind the next lob_reset acts on it; the environment's latest getState() is in the record)
+        const uint64_t ctr = dst->recs[d].rng_ctr;
+        dst->recs[d] = src->recs[s];
+        dst->recs[d].rng_ctr = ctr;
+        dst->recs[d].book.n_traces = (int)dst->traces[d].nonzero.size();
+    }
+    return 0;
+}
+// getState() and getReward() of every book as the environment stands now, nothing recorded: what lob_get_state / lob_get_reward
+// evaluate (after ClearInventory the position, and with it the state, has moved on from the last record).  Books first .. first + n - 1,
+// which must have been initialised (oracle_reset, or a copy of such a book); vars: float [n][LOB_MAX_VARS].
+void oracle_state_now(oracle_learner* o, int32_t first, int32_t n, float* vars, double* reward) {
+    for (int b = 0; b < n; b++) {
+        std::vector<float> v;
+        o->env[first + b]->getState(v);
+        reward[b] = o->env[first + b]->getReward();
+        for (int i = 0; i < LOB_MAX_VARS; i++) vars[(size_t)b * LOB_MAX_VARS + i] = i < (int)v.size() ? v[i] : 0.0f;
+    }
 }
 
 int oracle_clear_inventory(oracle_learner* o) {
@@ -1505,6 +1554,9 @@ int oracle_set_rho(oracle_learner* o, const double* in, int32_t n) {
     return 0;
 }
 void oracle_get_rec(oracle_learner* o, int32_t book, oracle_step_rec* out) { *out = o->recs[book]; }
+void oracle_get_recs(oracle_learner* o, int32_t first, int32_t n, oracle_step_rec* out) {
+    for (int i = 0; i < n; i++) out[i] = o->recs[first + i];
+}
 double* oracle_theta(oracle_learner* o, int32_t which) { return o->theta[which].data(); }
 double* oracle_theta_b(oracle_learner* o, int32_t which) { return o->theta_b.empty() ? nullptr : o->theta_b[which].data(); }
 int32_t oracle_get_traces(oracle_learner* o, int32_t b, int32_t* idx, float* e, int32_t cap) {

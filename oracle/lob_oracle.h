@@ -62,7 +62,17 @@ int32_t oracle_model_log(oracle_learner* o, double* rows, int32_t cap);
 int oracle_td_step_begin(oracle_learner* o);
 int oracle_td_step_end(oracle_learner* o);
 int oracle_eval_step(oracle_learner* o, int32_t n_steps);  /* n x Backtester::_step */
-int oracle_env_step(oracle_learner* o, const int32_t* actions); /* performAction only */
+int oracle_env_step(oracle_learner* o, const int32_t* actions); /* performAction only; an action outside [0, 9) skips the book (lob_vec_step) */
+/* The environment side of book src_idx[i] of `src` (environment, done flag, last record) becomes that of book
+ * dst_idx[i] of `dst`, i = 0 .. n - 1 in order; the target's learner (weights, traces, random counter, its two State objects) stays.  Same environment
+ * parameters in both oracles.  What lob_snapshot_restore puts back and what a branch holds (tests/vec_model.py); pinned against a
+ * replay by tests/test_vec_model.py.  -1: an index out of range. */
+int oracle_copy_books(oracle_learner* dst, const int32_t* dst_idx, oracle_learner* src, const int32_t* src_idx, int32_t n);
+/* getState() (float [n][LOB_MAX_VARS]) and getReward() (double [n]) of the environments of books first .. first + n - 1 as they stand,
+ * nothing recorded; the books must have been initialised (oracle_reset, or a copy of such a book) */
+void oracle_state_now(oracle_learner* o, int32_t first, int32_t n, float* vars, double* reward);
+/* oracle_get_rec for books first .. first + n - 1 */
+void oracle_get_recs(oracle_learner* o, int32_t first, int32_t n, oracle_step_rec* out);
 int oracle_clear_inventory(oracle_learner* o);
 int oracle_handle_terminal(oracle_learner* o);
 void oracle_set_alpha(oracle_learner* o, double a);

@@ -738,6 +738,14 @@ __global__ void __launch_bounds__(256) clear_inventory_kernel(const DevParams* _
     env_load(S, b, e);
     clear_inventory(c, e);
     env_store(S, b, e);
+    // Slot 2 mirrors the latest getState() -- lob_eval_step acts on it (Backtester::_step extracts the state itself before acting),
+    // lob_vec_step hands it to a book it does not step -- and the position has just moved.  A book that is out of data keeps the
+    // state of its last completed step (vec_observe_derive_kernel's rule).  The learner's two State objects are not touched.
+    if (S.done[b] != 2) {
+        f32* vf = S.vars + ((size_t)b * 3 + 2) * 16;
+        const Track tk = state_track(c, e);
+        for (int i = 0; i < P.V; i++) vf[i] = (f32)get_variable(c, e, P.vars[i], tk);
+    }
 }
 #endif
 

@@ -71,6 +71,10 @@ def load():
     lib.oracle_set_rho.restype = C.c_int
     lib.oracle_set_rho.argtypes = [vp, vp, C.c_int32]
     lib.oracle_get_rec.argtypes = [vp, C.c_int32, P(StepRec)]
+    lib.oracle_get_recs.argtypes = [vp, C.c_int32, C.c_int32, vp]
+    lib.oracle_copy_books.restype = C.c_int
+    lib.oracle_copy_books.argtypes = [vp, vp, vp, vp, C.c_int32]
+    lib.oracle_state_now.argtypes = [vp, C.c_int32, C.c_int32, vp, vp]
     lib.oracle_theta.restype = P(C.c_double)
     lib.oracle_theta.argtypes = [vp, C.c_int32]
     lib.oracle_theta_b.restype = P(C.c_double)
@@ -163,7 +167,27 @@ class Oracle:
         return np.frombuffer(bytes(r), dtype=STEP_DTYPE)[0]
 
     def recs(self):
-        return np.array([self.rec(b) for b in range(self.B)], dtype=STEP_DTYPE)
+        out = np.zeros(self.B, dtype=STEP_DTYPE)
+        self.lib.oracle_get_recs(self.h, 0, self.B, ptr(out))
+        return out
+
+    def copy_books(self, dst_idx, src, src_idx):
+        """oracle_copy_books: the environment side of book src_idx[i] of the oracle `src` becomes that of book dst_idx[i] here."""
+        d = np.ascontiguousarray(dst_idx, dtype=np.int32).reshape(-1)
+        s = np.ascontiguousarray(src_idx, dtype=np.int32).reshape(-1)
+        assert d.shape == s.shape
+        assert self.lib.oracle_copy_books(self.h, ptr(d), src.h, ptr(s), d.shape[0]) == 0, "oracle_copy_books"
+        if src is not self:   # (the copies read the source's records: its buffers must outlive this oracle's use of them)
+            self._src_bufs = getattr(self, "_src_bufs", {})
+            self._src_bufs[id(src)] = (src.records, getattr(src, "_day_bufs", ()))
+
+    def state_now(self, first=0, n=None):
+        """oracle_state_now: (getState() float32 [n, LOB_MAX_VARS], getReward() float64 [n]) of the environments of books first ..
+        first + n - 1 as they stand (initialised books only)."""
+        n = self.B - first if n is None else n
+        v, r = np.zeros((n, abi.LOB_MAX_VARS), np.float32), np.zeros(n, np.float64)
+        self.lib.oracle_state_now(self.h, first, n, ptr(v), ptr(r))
+        return v, r
 
     def theta(self, which=0):
         p = self.lib.oracle_theta(self.h, which)

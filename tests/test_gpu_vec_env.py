@@ -472,3 +472,76 @@ def test_learner_steps_after_vec_steps(algo):
     dev.free()
     eng.close()
     orc.close()
+
+
+@pytest.mark.parametrize("algo", [abi.ALGO_SARSA, abi.ALGO_QLAMBDA], ids=["sarsa", "qlambda"])
+def test_learner_steps_behind_greedy_steps_skipped_books_and_dry_books(algo):
+    """Named regression cases of tests/test_gpu_call_sequences.py (NOTES.md, the call sequences): learner steps, private theta, exact,
+      a. behind lob_eval_step in the same episode -- reset, eval_step, td_step_begin + _end was the reduced list: the greedy step
+         leaves the state behind it in the learner's `state` object, as lob_step and lob_vec_step do (include/lob_engine.h
+         lob_eval_step), and the learner step acts on it;
+      b. behind a lob_vec_step that skipped books (actions out of range) and behind a mid-episode lob_clear_inventory;
+      c. behind vec steps in which books ran out of data -- reset, vec steps to the first dry book, td_step_begin + _end: those
+         books keep their traces, and the record says so."""
+    B = 48
+    p = make_params(5, 2, algo=algo)
+    V = p.n_vars
+    rec = engine.gen_stream_host(gen(160), 5, 2, 0, B)
+    eng = engine.Engine(p, B)
+    eng.load_events(rec)
+    orc = ol.Oracle(p, rec)
+    dev = DevVec(B, V)
+    eng.reset()
+    orc.reset()
+    rng = np.random.default_rng(9)
+
+    def vec(n, p_skip):
+        for _ in range(n):
+            a = rng.integers(0, abi.LOB_N_ACTIONS, size=B).astype(np.int32)
+            a[rng.random(B) < p_skip] = -1
+            dev.step(eng, a)
+            orc.env_step(a)
+        return dev.read(eng)
+
+    def learner(n, tag, split=False):
+        for step in range(n):
+            if split and eng.td_split_supported():
+                eng.td_step_begin()
+                eng.td_step_end()
+                orc.td_step_begin()
+                orc.td_step_end()
+            else:
+                eng.td_step(1)
+                orc.td_step(1)
+            compare_learner_step(eng, orc, "%s, learner step %d" % (tag, step))
+
+    learner(3, "at the start")
+    eng.eval_step(2)
+    orc.eval_step(2)
+    learner(3, "behind two greedy steps", split=True)
+    vec(4, 0.2)
+    learner(3, "behind vec steps that skipped books")
+    eng.clear_inventory()
+    orc.clear_inventory()
+    # d. a greedy step behind a mid-episode lob_clear_inventory chooses its action in the state with the new position (reduced list:
+    #    reset, eval_step, clear_inventory, eval_step): clear_inventory_kernel refreshes the latest getState()
+    eng.eval_step(1)
+    orc.eval_step(1)
+    compare_env(eng, orc, "a greedy step behind lob_clear_inventory")
+    np.testing.assert_array_equal(eng.last_actions(), orc.recs()["action"])
+    np.testing.assert_array_equal(eng.rng_counters(), orc.recs()["rng_ctr"])
+    learner(2, "behind lob_clear_inventory and a greedy step", split=True)
+    eng.eval_step(1)
+    orc.eval_step(1)
+    for _ in range(60):
+        got = vec(1, 0.1)
+        if (got["terminal"] == 2).any():
+            break
+    assert (got["terminal"] == 2).any() and (got["terminal"] == 0).any(), "some books have run dry in a vec step, others are live"
+    learner(3, "behind vec steps in which books ran dry", split=True)
+    assert eng.vec_status()[0] == abi.LOB_EINVAL, "the skipped books were counted"
+    for b in range(0, B, 9):
+        np.testing.assert_array_equal(eng.theta(b), orc.theta(b))
+    dev.free()
+    eng.close()
+    orc.close()

@@ -1,0 +1,283 @@
+"""The model of the vector-env interface (tests/vec_model.py) and its sequence generator (tests/vec_sequences.py), on the CPU:
+
+  a. oracle_copy_books against a replay: a copied book continues bit for bit like a fresh oracle replayed with the same days and
+     actions -- across a lob_reset too, where a replay of the present episode alone does NOT (quirk Q7: the window sums persist),
+     which is why the model keeps books and not per-episode journals;
+  b. the learner-phase premise: oracle_env_step with the actions a learner step took reproduces the book's environment after it;
+  c. the model against a plain batched oracle: up to the first restore of a sequence its real books are the batched oracle's, byte
+     for byte at every operation, whatever saves, look-aheads, forks, branch steps and refused calls stand in between;
+  d. the refusal texts are the rows of tests/test_gpu_refusal_matrix.py;
+  e. coverage of the default seeds: conditions on the INPUTS of tests/test_gpu_call_sequences.py (if one fails, change the generator's
+     weights, not the assertion), the variant axes, and the model's wall time per sequence, which bounds that test's CPU share."""
+import collections
+import os
+import time
+
+import numpy as np
+import pytest
+
+from rl_markets_amd import abi, engine
+from tests import oracle_lib as ol
+from tests import test_gpu_refusal_matrix as matrix
+from tests import vec_model
+from tests.test_gpu_vec_env import gen, make_params
+from tests.test_oracle_days import make_days
+from tests.vec_sequences import NEVER_REFUSED, Sequence, Variant
+
+N_SEEDS = 24
+REAL_MOVES = ("reset", "days_set", "days_select", "vec_step", "clear_inventory", "td_step", "eval_step", "td_begin", "td_end")
+
+
+def env_fields(rec):
+    """What a copy carries of a record: everything but the learner's words (td, random counter, trace count)."""
+    book = rec["book"].copy()
+    book["n_traces"] = 0
+    return rec["action"].tobytes() + rec["reward"].tobytes() + rec["vars"].tobytes() + book.tobytes()
+
+
+# ---- a. copy == replay ------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("normed", [False, True], ids=["pnl", "normed-3"])
+def test_copy_continues_like_a_replay(normed):
+    B, lengths = 5, (160, 100, 130)
+    p = make_params(5, 2, 1 << 12)
+    if normed:
+        p.reward_measure, p.lb_pnl = abi.REWARD_NORMED, 3
+    days = make_days(lengths)
+    lib = ol.DayLibrary(days)
+    p_env = abi.Params.from_buffer_copy(bytes(p))
+    p_env.theta_mode = abi.THETA_SHARED
+    rng = np.random.default_rng(5)
+    plan = [(rng.integers(0, 3, size=B), [rng.integers(-1, vec_model.NA + 1, size=B).astype(np.int32) for _ in range(n)]) for n in (25, 18)]
+
+    def play(o, upto_episode, upto_step):
+        for ep, (day, acts) in enumerate(plan[:upto_episode + 1]):
+            o.set_days(*lib.of(day))
+            o.reset()
+            for a in acts[:upto_step if ep == upto_episode else len(acts)]:
+                o.env_step(a)
+            if ep < upto_episode:
+                o.clear_inventory()
+
+    new = lambda: ol.Oracle(p, np.stack([days[0]] * B))   # noqa: E731
+    a = new()
+    play(a, 1, 9)                                           # two episodes, nine steps into the second
+    # a copy into an oracle of another size and weight mode, books shuffled ...
+    c = ol.Oracle(p_env, np.zeros((2 * B, 2, days[0].shape[1]), np.uint32))
+    perm = rng.permutation(B).astype(np.int32)
+    c.copy_books(B + np.arange(B, dtype=np.int32), a, perm)
+    # ... a replay from nothing, and a replay of the second episode alone on a fresh oracle
+    r = new()
+    play(r, 1, 9)
+    fresh = new()
+    fresh.set_days(*lib.of(plan[1][0]))
+    fresh.reset()
+    for act in plan[1][1][:9]:
+        fresh.env_step(act)
+    differs = False
+    for step in range(9, 18):
+        for b in range(B):
+            assert env_fields(c.recs()[B + b]) == env_fields(r.recs()[perm[b]]), "step %d book %d: the copy against the replay" % (step, b)
+        assert a.recs().tobytes() == r.recs().tobytes()
+        differs |= any(env_fields(fresh.recs()[b]) != env_fields(r.recs()[b]) for b in range(B))
+        act = plan[1][1][step]
+        a.env_step(act)
+        r.env_step(act)
+        fresh.env_step(act)
+        pad = np.full(2 * B, -1, np.int32)
+        pad[B:] = act[perm]
+        c.env_step(pad)
+    v1, w1 = c.state_now(B, B)
+    v2, w2 = r.state_now()
+    assert v1.tobytes() == v2[perm].tobytes() and w1.tobytes() == w2[perm].tobytes()
+    assert (r.recs()["book"]["total_ticks"] > 5).all()
+    if normed:
+        assert differs, "the second episode alone on a fresh oracle parts from the whole history: the PnL windows' sums persist"
+    # a copy back over books that moved on puts them back: the masked restore
+    a.env_step(plan[1][1][17])
+    a.copy_books(np.array([0, 3], np.int32), c, B + np.array([int(np.flatnonzero(perm == 0)[0]), int(np.flatnonzero(perm == 3)[0])], np.int32))
+    for b in (0, 3):
+        assert env_fields(a.recs()[b]) == env_fields(r.recs()[b])
+    for o in (a, c, r, fresh):
+        o.close()
+
+
+# ---- b. the learner-phase premise -------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("algo", [abi.ALGO_QLAMBDA, abi.ALGO_SARSA], ids=["qlambda", "sarsa"])
+def test_env_steps_with_the_learners_actions_reproduce_its_books(algo):
+    """Every field of the book, getState() and getReward(), at every step, for every book that has data left.  The one exception: a
+    learner step that runs out of data has placed its orders first and records no action, so the book it leaves behind (terminal 2)
+    cannot be replayed from the record -- which is why the model steps the learner in the very oracle that holds the books."""
+    B = 7
+    p = make_params(5, 2, 1 << 12, algo)
+    rec = engine.gen_stream_host(gen(160, "dry", p), 5, 2, 0, B)
+    learner, env = ol.Oracle(p, rec), ol.Oracle(p, rec)
+    learner.reset()
+    env.reset()
+    steps = 0
+    while learner.counters()[2] > 0:
+        before = learner.recs()["book"]["terminal"]
+        ticks = learner.recs()["book"]["total_ticks"].copy()
+        (learner.td_step if steps % 3 else learner.eval_step)(1)
+        lr = learner.recs()
+        stepped = (before == 0) & (lr["book"]["terminal"] != 2)
+        np.testing.assert_array_equal(lr["book"]["total_ticks"][stepped], ticks[stepped] + 1)
+        env.env_step(np.where(stepped, lr["action"], np.where(before == 0, 0, -1)).astype(np.int32))
+        er = env.recs()
+        (ev, ew), (lv, lw) = env.state_now(), learner.state_now()
+        for b in np.flatnonzero(lr["book"]["terminal"] != 2):
+            eb, lb = er["book"][b].copy(), lr["book"][b].copy()
+            eb["n_traces"] = lb["n_traces"] = 0
+            assert eb.tobytes() == lb.tobytes(), "step %d book %d: book" % (steps, b)
+            assert ev[b].tobytes() == lv[b].tobytes() and ew[b].tobytes() == lw[b].tobytes(), "step %d book %d: getState / getReward" % (steps, b)
+            if steps % 3:   # (lob_eval_step records the state its action was chosen in, the Backtester's order: the state before the step)
+                assert er["vars"][b].tobytes() == lr["vars"][b].tobytes(), "step %d book %d: the recorded state" % (steps, b)
+        steps += 1
+        assert steps < 400
+    assert steps > 30 and (learner.recs()["book"]["terminal"] == 2).all()
+    learner.close()
+    env.close()
+
+
+# ---- c. the model against a plain batched oracle -------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("seed", [2, 11, 13, 20])
+def test_model_against_the_batched_oracle(seed):
+    seq = Sequence(seed)
+    m = seq.m
+    rec, days = seq.v.data()
+    plain = ol.Oracle(seq.v.params(), rec if days is None else np.stack([days[0]] * m.B))
+    lib = ol.DayLibrary(days) if days is not None else None
+    compared = moved = 0
+    for i, kind, args, want in seq:
+        if kind == "restore" and not want.refused:
+            break
+        if kind in REAL_MOVES and not want.refused:
+            moved += 1
+            if kind == "reset":
+                if lib is not None:
+                    plain.set_days(*lib.of(m.day_cur))
+                plain.reset()
+            elif kind == "vec_step":
+                for a in args["actions"]:
+                    plain.env_step(a)
+            elif kind == "clear_inventory":
+                plain.clear_inventory()
+            elif kind in ("td_step", "eval_step"):
+                getattr(plain, kind)(args["n"])
+            elif kind == "td_begin":
+                plain.td_step_begin()
+            elif kind == "td_end":
+                plain.td_step_end()
+        if m.was_reset and not m.half_open:
+            assert m.real.recs().tobytes() == plain.recs().tobytes(), "seed %d op %d (%s)" % (seed, i, seq.log[-1])
+            c = plain.counters()
+            assert (m.steps, m.events) == (int(c[0]), int(c[1])), "seed %d op %d: counters" % (seed, i)
+            compared += 1
+    assert compared > 10 and moved > 5, (compared, moved)
+    plain.close()
+    m.close()
+
+
+# ---- d. the refusal texts ----------------------------------------------------------------------------------------------------------
+
+def test_refusal_texts_are_the_matrix_rows():
+    for name in ("R", "H", "S", "OFF", "NOLIB", "NOSTEP"):
+        assert getattr(vec_model, name) == getattr(matrix, name), name
+    col = {s: i for i, s in enumerate(matrix.STATES)}
+    rows = {case: (fn, expect) for case, fn, expect in matrix.TABLE}
+    kind_of = {"lob_vec_step": "vec_step", "lob_vec_observe": "observe", "lob_vec_book": "book", "lob_vec_history": "history",
+               "lob_vec_peek": "peek", "lob_vec_rollout": "rollout", "lob_snapshot_save": "save", "lob_clear_inventory": "clear_inventory",
+               "lob_episode_stats": "stats", "lob_td_step": "td_step", "lob_td_step_begin": "td_begin", "lob_td_step_end": "td_end",
+               "lob_eval_step": "eval_step", "lob_step_log_enable": "log_enable", "lob_step_log_counts off": "log_counts",
+               "lob_step_log_read off": "log_read", "lob_days_select no lib": "days_select", "lob_days_set no lib": "days_set"}
+    a = {"vec_step": {"actions": np.zeros((1, 3), np.int32)}, "history": {"K": 1}, "peek": {"mask": 1},
+         "rollout": {"plans": np.zeros((1, 1, 3), np.int32), "gamma": 1.0}, "save": {"slot": 0, "mask": None}, "stats": {"by_day": False},
+         "td_step": {"n": 1}, "eval_step": {"n": 1}, "log_enable": {"sel": None, "cap": 4}, "days_select": {"mode": 1, "first": 0, "n": 1},
+         "days_set": {"days": np.zeros(3, np.int32)}}
+    p = make_params(5, 2, 1 << 10)
+    rec = engine.gen_stream_host(gen(160, "dry", p), 5, 2, 0, 3)
+    checked = 0
+    for state in ("fresh", "reset", "mid", "restored"):
+        m = vec_model.Model(p, 3, records=rec)
+        if state != "fresh":
+            m.apply("reset")
+            m.apply("save", slot=0, mask=None)
+        if state == "mid":
+            m.apply("td_begin")
+        if state == "restored":
+            m.apply("restore", slot=0, mask=None)
+        for case, kind in kind_of.items():
+            fn, expect = rows[case]
+            ref = m.refusal(kind, **a.get(kind, {}))
+            want = expect[col[state]]
+            if want is matrix.OK:
+                assert ref is None, (case, state, ref)
+            else:
+                assert ref is not None and (ref.rc, ref.err) == (abi.LOB_ESTATE, fn + want), (case, state, ref)
+            checked += 1
+        m.close()
+    assert checked == 4 * len(kind_of)
+
+
+# ---- e. coverage of the default seeds -----------------------------------------------------------------------------------------------
+
+def test_variant_axes():
+    vs = [Variant(s) for s in range(N_SEEDS)]
+    for axis, values in (("B", (3, 65, 130)), ("depth", (5, 10)), ("trades", (2, 3)), ("normed", (False, True)), ("days", (False, True)),
+                         ("ending", ("dry", "session")), ("env16_off", (False, True))):
+        count = collections.Counter(getattr(v, axis) for v in vs)
+        assert set(count) == set(values) and min(count.values()) >= 4, (axis, dict(count))
+    assert abs(sum(v.env16_off for v in vs) - N_SEEDS / 3) <= 1, "LOB_ENV16_MAX=0 on a third of the seeds"
+    assert sum(v.B == 130 and v.days for v in vs) >= 2 and sum(v.B == 130 and v.normed for v in vs) >= 2
+
+
+def test_coverage_of_the_default_seeds():
+    legal, refused, seen, times = collections.Counter(), collections.Counter(), collections.Counter(), []
+    episodes = []
+    for seed in range(int(os.environ.get("LOB_SEQ_SEEDS", N_SEEDS))):
+        t0 = time.perf_counter()
+        seq = Sequence(seed)
+        n_ops = 0
+        for i, kind, args, want in seq:
+            n_ops += 1
+            if want.refused:
+                refused[kind] += 1
+                seen["branch calls on a set voided by lob_reset"] += kind in ("bstep", "select") and seq.m.branch == "void" and not seq.m.half_open
+                continue
+            legal[kind] += 1
+            b, o = want.before, want.out
+            seen["restores that revive a book"] += kind == "restore" and o["revived"] > 0
+            seen["selects whose parents differ between books"] += kind == "select" and o["differs_between_books"]
+            seen["branch steps with some branches over and some live"] += kind == "bstep" and o["some_over_some_live"]
+            seen["forks after a restore in the same episode"] += kind == "fork" and b["restored"]
+            seen["resets with a live branch set and a full slot"] += kind == "reset" and b["branch"] == "live" and b["full"]
+            seen["forks that need a larger set"] += kind == "fork" and o["grown"]
+            seen["statistics after a restore"] += kind == "stats" and b["restored"]
+        dt = time.perf_counter() - t0
+        times.append(dt)
+        episodes.append(seq.m.episode)
+        assert 60 <= n_ops <= 90
+        assert 3 * seq.stats["all_over_ops"] <= n_ops, "seed %d spends %d of %d ops with every book over" % (seed, seq.stats["all_over_ops"], n_ops)
+        print("seed %2d  %-44s %2d ops  %d episodes  model %.2f s" % (seed, seq.v.label(), n_ops, seq.m.episode, dt))
+        seq.m.close()
+    print("%-18s %6s %8s" % ("kind", "legal", "refused"))
+    for k in vec_model.KINDS:
+        print("%-18s %6d %8d" % (k, legal[k], refused[k]))
+    for k, n in seen.items():
+        print("%-52s %d" % (k, n))
+    print("ops %d, model time per sequence: max %.2f s, mean %.2f s" % (sum(legal.values()) + sum(refused.values()), max(times), np.mean(times)))
+    if len(times) < N_SEEDS:
+        return
+    for k in vec_model.KINDS:
+        assert legal[k] >= 20, "%s: legal %d times" % (k, legal[k])
+        assert refused[k] >= 3 or k in NEVER_REFUSED, "%s: refused %d times" % (k, refused[k])
+    floor = {"restores that revive a book": 10, "selects whose parents differ between books": 10,
+             "branch steps with some branches over and some live": 10, "forks after a restore in the same episode": 5,
+             "resets with a live branch set and a full slot": 5, "forks that need a larger set": 5, "statistics after a restore": 5,
+             "branch calls on a set voided by lob_reset": 8}
+    for k, n in floor.items():
+        assert seen[k] >= n, "%s: %d" % (k, seen[k])
+    assert np.mean([2 <= e <= 3 for e in episodes]) >= 0.75, episodes
+    assert max(times) < 5.0, "a sequence's model time bounds the GPU test's CPU share"
