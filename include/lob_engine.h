@@ -725,6 +725,32 @@ int lob_branch_step  (lob_engine* e, const int32_t* dev_actions /* [N][B] */, co
 int lob_branch_select(lob_engine* e, const int32_t* dev_parent  /* [N][B] */, const lob_branch_out* out /* may be NULL */);
 int lob_branch_close (lob_engine* e);
 
+/* ---- branch sets: the order book and the event window of every branch ---
+ * lob_branch_out carries what the engine's own tile-coded agent reads.  A network that reads the book's levels, its own orders and
+ * inventory (lob_vec_book) and a window of the last K event records (lob_vec_history) gets the same two observations at every
+ * branch's state here, so that it can choose the actions of a closed loop over a branch set.  The two out-structs of the real books
+ * are reused; every tensor is branch-major as in lob_branch_out, N = the live set's n_branches, plane n = elements [n * n_books,
+ * (n + 1) * n_books), no padding:
+ *     lob_branch_book:    levels [N][B][4][depth], own [N][B][LOB_VEC_OWN_WORDS], time_ms [N][B]
+ *     lob_branch_history: levels [N][B][K][4][depth], trades [N][B][K][2][max_trades], time_ms [N][B][K], n_valid [N][B], rec [N][B]
+ *   ONE rule: element [n][b] is, bit for bit, what lob_vec_book / lob_vec_history(K) would write at [b] had the engine's books been in
+ * branch n's state -- for every branch, whatever its terminal word; behind lob_branch_fork, behind any lob_branch_step (an action
+ * out of range, a "stay", included) and behind lob_branch_select, in the new arrangement.  Every rule of the two calls carries over:
+ * `depth` levels, zeros where there is no snapshot, own in LOB_OWN_* order, time_ms copied as int64; history slots with a negative
+ * record index all zero, n_valid = min(K, rec + 1), rec never past the last record of THAT BOOK's stream (a replayed stream's phase,
+ * the day the book is playing) -- branches of one book differ in rec, not in the stream; every element of every non-NULL tensor is
+ * written on every call; any 1 <= K <= LOB_MAX_HISTORY is valid.
+ *   Each call is one launch enqueued on the engine's stream (lob_stream): no host read, no allocation, no copy and no
+ * synchronisation.  Nothing of the engine and nothing of the set changes.  Allowed after lob_snapshot_restore, while the step log
+ * records and while the real books step on.  LOB_EINVAL: a NULL engine, a NULL out, K outside [1, LOB_MAX_HISTORY]; a struct whose
+ * members are all NULL is LOB_OK and launches nothing.  LOB_ESTATE, with a message naming the call: before the first lob_reset,
+ * between lob_td_step_begin and lob_td_step_end, on a stream whose market track is a ring (no set can be forked there), and with no
+ * live set -- never forked, voided by lob_reset, closed.  A refused call writes nothing.
+ *   Not offered: the book and the window at the leaves of lob_vec_peek / lob_vec_rollout -- those launches keep no end state; a
+ * leaf's book is a branch set stepped under the plan. */
+int lob_branch_book   (lob_engine* e, const lob_vec_book_out* out);
+int lob_branch_history(lob_engine* e, int32_t K, const lob_vec_hist_out* out);
+
 /* ---- episode statistics of the whole batch ---------------------------------
  * What the reference logs about ONE environment after an episode -- the `training_log` row of Runner::RunEpisode
  * (src/experiment/serial.cpp:81-88: getEpisodeReward, getEpisodePnL, total_ticks), Base::writeStats and getTotalTransactions

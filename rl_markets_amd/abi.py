@@ -296,6 +296,8 @@ def load():
         "lob_branch_step": (C.c_int, [vp, vp, P(BranchOut)]),
         "lob_branch_select": (C.c_int, [vp, vp, P(BranchOut)]),
         "lob_branch_close": (C.c_int, [vp]),
+        "lob_branch_book": (C.c_int, [vp, P(VecBookOut)]),
+        "lob_branch_history": (C.c_int, [vp, C.c_int32, P(VecHistOut)]),
         "lob_snapshot_save": (C.c_int, [vp, C.c_int32, C.c_void_p]),
         "lob_snapshot_restore": (C.c_int, [vp, C.c_int32, C.c_void_p]),
         "lob_snapshot_free": (C.c_int, [vp, C.c_int32]),

@@ -272,6 +272,7 @@ constexpr unsigned lob_vec_step = RESET | WHOLE_STEP, lob_vec_observe = RESET | 
 constexpr unsigned lob_vec_book = RESET | WHOLE_STEP, lob_vec_history = RESET | WHOLE_STEP, lob_vec_act = RESET | WHOLE_STEP;
 constexpr unsigned lob_vec_peek = RESET | WHOLE_STEP | NO_RING, lob_vec_rollout = RESET | WHOLE_STEP | NO_RING;
 constexpr unsigned lob_branch_fork = RESET | WHOLE_STEP | NO_RING, lob_branch_step = RESET | WHOLE_STEP | NO_RING, lob_branch_select = RESET | WHOLE_STEP | NO_RING;
+constexpr unsigned lob_branch_book = lob_branch_step, lob_branch_history = lob_branch_step;
 constexpr unsigned lob_vec_features = WHOLE_STEP, lob_vec_update = WHOLE_STEP;   // (+ RESET behind it when the rows are the books')
 constexpr unsigned lob_snapshot_save = RESET | WHOLE_STEP | NO_RING_BACK, lob_snapshot_restore = RESET | WHOLE_STEP | NO_RING_BACK;
 constexpr unsigned lob_get_state = RESET, lob_get_reward = RESET, lob_get_terminal = RESET;

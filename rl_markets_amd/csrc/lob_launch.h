@@ -1,9 +1,9 @@
-// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is fifteen
+// Launch entry points of the kernel families that are compiled in translation units of their own (the engine library is sixteen
 // .hip files with kernels, built in parallel with three that hold host code only -- lob_tu_host_streams.hip, lob_tu_host_vec.hip,
 // lob_tu_host_reads.hip: the C ABI's families that launch through this header alone, lob_engine_impl.h --: lob_engine.hip -- the
 // engine object, the step pipeline, the weights and the update / memo / trace kernels --, lob_tu_env.hip,
 // lob_tu_prepass.hip, lob_tu_learn.hip, lob_tu_stats.hip, lob_tu_steplog.hip, lob_tu_vec.hip, lob_tu_vecbook.hip, lob_tu_vechist.hip, lob_tu_snapshot.hip,
-// lob_tu_vecact.hip, lob_tu_vecfeat.hip, lob_tu_vecpeek.hip, lob_tu_vecroll.hip, lob_tu_branch.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
+// lob_tu_vecact.hip, lob_tu_vecfeat.hip, lob_tu_vecpeek.hip, lob_tu_vecroll.hip, lob_tu_branch.hip, lob_tu_branchobs.hip).  Plain host functions: which instantiation runs is decided here, by the same rules
 // lob_engine.hip used when it held the launches itself.  Kernels measured and lost (NOTES.md "Round 4") are only compiled with
 // -DLOB_EXPERIMENTS (tools/exp_variants.sh); a product build answers LOB_EXPERIMENTS-only requests with the product kernel.
 #ifndef LOB_LAUNCH_H
@@ -272,6 +272,26 @@ void lobk_branch_fork(hipStream_t st, const DevParams* Pd, const DevState& S, co
 void lobk_branch_step(hipStream_t st, bool t2, const DevParams* Pd, const DevState& S, const BranchSrc& a);
 // branch_select_kernel: n_branches * Bpad / 64 one-wave blocks
 void lobk_branch_select(hipStream_t st, const DevParams* Pd, const BranchSrc& a);
+
+// ---- lob_tu_branchobs.hip ----
+// What lob_branch_book / lob_branch_history (include/lob_engine.h) read, as kernel arguments: the LIVE buffer of the set (lob_branch.h:
+// the field words of branch n of book b at lane n * Bpad + b), and what VecBookSrc / VecHistSrc name of the engine -- the event records,
+// the first record and the length of every BOOK's stream (indexed by b, never by the lane) and the words of a record at which its
+// arrays start.  Outputs are branch-major: row n * B + b, no padding to Bpad.
+struct BranchObsSrc {
+    BranchSet set;             // the live buffer
+    const uint32_t* records;   // DevState::records / rec_phase (null: book b's stream starts at record b * n_events)
+    const i64* rec_phase;
+    const i32* rec_len;        // DevState::rec_len (null: every stream has n_events records)
+    i32 n_events, Wd, D, T;
+    i32 w_ask_px, w_ask_vol, w_bid_px, w_bid_vol, w_trades;
+    i32 B, Bpad;               // books; B rounded up to a multiple of 64
+    i32 n_branches;
+};
+// branch_book_kernel: n_branches * Bpad / 64 blocks of LOB_VECBOOK_BLOCK threads, block i branch i / (Bpad / 64)
+void lobk_branch_book(hipStream_t st, const BranchObsSrc& s, const lob_vec_book_out& out);
+// branch_hist_kernel: a block per LOB_VECHIST_ROWS rows of the flat [n_branches x B x K] row space
+void lobk_branch_history(hipStream_t st, const BranchObsSrc& s, int K, const lob_vec_hist_out& out);
 
 // ---- lob_tu_learn.hip ----
 // learn_q_pair_kernel / learn_q_lane_kernel<algo, vt, tr>: vt = 8 when the state has eight variables (else 0)

@@ -325,6 +325,58 @@ int lob_branch_select(lob_engine* e, const int32_t* dev_parent, const lob_branch
     return LOB_OK;
 }
 
+// ---- the book and the event window of every branch (include/lob_engine.h lob_branch_book / lob_branch_history; lob_tu_branchobs.hip;
+// DESIGN.md 7m) ----
+// What the two kernels read: the buffer e->branch_cur designates -- lob_branch_select flips it -- and of the engine what lob_vec_book /
+// lob_vec_history read, e->S.records as it is now.
+static BranchObsSrc branch_obs_src(lob_engine* e) {
+    const BranchSrc a = branch_src(e, e->branch_n, e->branch_cur);
+    BranchObsSrc s;
+    memset(&s, 0, sizeof s);
+    s.set = a.set;
+    s.records = e->S.records; s.rec_phase = e->S.rec_phase; s.rec_len = e->S.rec_len;
+    s.n_events = e->S.n_events; s.Wd = e->P.Wd; s.D = e->P.D; s.T = e->P.T;
+    s.w_ask_px = drec_ask_px(e->P.D, e->P.T); s.w_ask_vol = drec_ask_vol(e->P.D, e->P.T);
+    s.w_bid_px = drec_bid_px(e->P.D, e->P.T); s.w_bid_vol = drec_bid_vol(e->P.D, e->P.T); s.w_trades = drec_trades(e->P.D, e->P.T);
+    s.B = a.B; s.Bpad = a.Bpad; s.n_branches = a.n_branches;
+    return s;
+}
+
+// lob_vec_book of every branch (branch_book_kernel): one launch on the engine's stream, nothing read back, nothing of the engine or of
+// the set changed.
+int lob_branch_book(lob_engine* e, const lob_vec_book_out* out) {
+    if (!e || !out) { lob_set_error("lob_branch_book: NULL argument"); return LOB_EINVAL; }
+    LOB_GUARD(e, lob_branch_book);
+    const int rc = branch_live_ok(e, "lob_branch_book");
+    if (rc) return rc;
+    if (!out->levels && !out->own && !out->time_ms) return LOB_OK;
+    HIPCHK(hipSetDevice(e->device));
+    {
+        TimedLaunch t(e, "branch_book_kernel", nullptr, true);
+        lobk_branch_book(e->stream, branch_obs_src(e), *out);
+    }
+    HIPCHK(hipGetLastError());
+    return LOB_OK;
+}
+
+// lob_vec_history(K) of every branch (branch_hist_kernel): one launch on the engine's stream, nothing read back, nothing of the engine
+// or of the set changed.
+int lob_branch_history(lob_engine* e, int32_t K, const lob_vec_hist_out* out) {
+    if (!e || !out) { lob_set_error("lob_branch_history: NULL argument"); return LOB_EINVAL; }
+    if (K < 1 || K > LOB_MAX_HISTORY) { lob_set_error("lob_branch_history: K = " + std::to_string(K) + " is outside [1, " + std::to_string(LOB_MAX_HISTORY) + "]"); return LOB_EINVAL; }
+    LOB_GUARD(e, lob_branch_history);
+    const int rc = branch_live_ok(e, "lob_branch_history");
+    if (rc) return rc;
+    if (!out->levels && !out->trades && !out->time_ms && !out->n_valid && !out->rec) return LOB_OK;
+    HIPCHK(hipSetDevice(e->device));
+    {
+        TimedLaunch t(e, "branch_hist_kernel", nullptr, true);
+        lobk_branch_history(e->stream, branch_obs_src(e), K, *out);
+    }
+    HIPCHK(hipGetLastError());
+    return LOB_OK;
+}
+
 int lob_branch_close(lob_engine* e) {
     if (!e) { lob_set_error("lob_branch_close: NULL engine"); return LOB_EINVAL; }
     e->branch_live = false;

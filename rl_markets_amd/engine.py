@@ -381,6 +381,20 @@ class Engine:
         """lob_branch_close: releases the branch set's buffers (waits for the engine's stream); close() does the same."""
         self._check(self.lib.lob_branch_close(self.h))
 
+    def branch_book(self, out):
+        """lob_branch_book: vec_book of every branch of the live set -- levels f32 [N, B, 4, depth], own f32 [N, B, 16], time_ms i64
+        [N, B] at the device addresses of `out` (abi.VecBookOut; 0 = not wanted), branch-major: [n, b] is bit for bit what vec_book
+        would write at [b] had the books been in branch n's state.  One launch on the engine's stream; nothing of the engine or of
+        the set changes."""
+        self._check(self.lib.lob_branch_book(self.h, C.byref(out)))
+
+    def branch_history(self, K, out):
+        """lob_branch_history: vec_history(K) of every branch of the live set -- levels f32 [N, B, K, 4, depth], trades f32 [N, B, K,
+        2, max_trades], time_ms i32 [N, B, K], n_valid and rec i32 [N, B] at the device addresses of `out` (abi.VecHistOut; 0 = not
+        wanted), branch-major: the window ends at the branch's own current record, within the book's own stream.  One launch on the
+        engine's stream; nothing of the engine or of the set changes."""
+        self._check(self.lib.lob_branch_history(self.h, int(K), C.byref(out)))
+
     def snapshot_save(self, slot, mask_ptr=None):
         """lob_snapshot_save: the environment state of the books selected by the DEVICE mask at address `mask_ptr` (uint8 [B],
         nonzero selects; None: every book, which (re)starts the slot) into snapshot slot `slot` (0 .. abi.MAX_SNAPSHOTS - 1);

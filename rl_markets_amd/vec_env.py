@@ -103,7 +103,22 @@ the parents a top-k gives -- and one step():
         beam = (total + gamma ** (h + 1) * value).topk(k, dim=0).indices    # the branches the next round descends from
         ret = total.gather(0, beam)
 
-Not available on a ring-mode stream.  A VecEnv that never calls branch() allocates and launches nothing for it.
+branch(n, book=True, history=K) also keeps the order book and the event window of every BRANCH on the device (lob_branch_book /
+lob_branch_history): .levels f32 [n, B, 4, D], .own f32 [n, B, 16], .time_ms i64 [n, B] and .hist_levels f32 [n, B, K, 4, D],
+.hist_trades f32 [n, B, K, 2, T], .hist_time_ms i32 [n, B, K], .hist_valid / .hist_rec i32 [n, B] -- per branch what the VecEnv's own
+tensors of those names would hold had the books been in that branch's state, refreshed behind every fork() / step() / select().  A
+torch network over the book and the window choosing the actions of a closed loop, where q_values() serves only the engine's own agent:
+
+    br = env.branch(n, book=True, history=K)
+    ret = torch.zeros((n, B), dtype=torch.float64, device=dev)
+    for h in range(H):
+        x = torch.cat([br.hist_levels.flatten(2), br.levels.flatten(2), br.own], dim=2)    # [n, B, K * 4 * D + 4 * D + 16]
+        a = net(x.view(n * B, -1)).argmax(-1).to(torch.int32).view(n, B)
+        br.step(a)
+        ret += gamma ** h * br.reward
+
+Not available on a ring-mode stream.  A VecEnv that never calls branch() allocates and launches nothing for it, and a branch set
+without the two options allocates and launches nothing for them.
 
 step() reads the actions from the tensor's device memory and writes into five persistent tensors (lob_vec_step,
 include/lob_engine.h): no copy to or from the host and no synchronisation.  The engine runs on a stream of its own; it is made
@@ -278,11 +293,12 @@ class VecEnv:
         self._on_engine(self.eng.vec_rollout, plans.data_ptr(), P, H, gamma, out, inputs=(plans,))
         return obs, reward, terminal, stepped, ret
 
-    def branch(self, n):
+    def branch(self, n, book=False, history=0):
         """lob_branch_fork: the engine's branch set (one per engine) remade as n (1 .. abi.MAX_BRANCHES) copies of every book's
         present state.  Returns a Branches object (its tensors are allocated here, the engine's buffers by the engine: the first
-        fork, and one that needs more room than any before, synchronises the device)."""
-        return Branches(self, n)
+        fork, and one that needs more room than any before, synchronises the device).  book / history (0 .. abi.MAX_HISTORY): the
+        set also keeps every branch's order book / last `history` event records on the device (Branches)."""
+        return Branches(self, n, book=book, history=history)
 
     def q_values(self, vars):
         """lob_vec_q: Q(s, .) under the engine's weights (theta; book 0's under private theta) for n free-standing states, f32 [n, V]
@@ -382,11 +398,27 @@ class VecEnv:
 
 class Branches:
     """A branch set of a VecEnv (VecEnv.branch): n private copies of every book's environment state, stepped and rearranged on the
-    device.  The engine holds one set: making another Branches, or fork() with it, remakes that set."""
+    device.  The engine holds one set: making another Branches, or fork() with it, remakes that set.
 
-    def __init__(self, env, n):
+    book=True: .levels f32 [n, B, 4, D], .own f32 [n, B, 16] and .time_ms i64 [n, B] (lob_branch_book); history=K (1 ..
+    abi.MAX_HISTORY): .hist_levels f32 [n, B, K, 4, D], .hist_trades f32 [n, B, K, 2, T], .hist_time_ms i32 [n, B, K], .hist_valid
+    and .hist_rec i32 [n, B] (lob_branch_history) -- [i, b] is what the VecEnv's tensor of that name would hold at [b] had the books
+    been in branch i's state.  Persistent tensors, refreshed right behind every fork(), step() and select() on the engine's stream,
+    ready wherever .obs is.  Without the options the attributes do not exist and nothing is allocated or launched for them.  A
+    network over the book and the window driving a closed loop:
+
+        br = env.branch(n, book=True, history=K)
+        for h in range(H):
+            x = torch.cat([br.hist_levels.flatten(2), br.levels.flatten(2), br.own], dim=2)
+            br.step(net(x.view(n * B, -1)).argmax(-1).to(torch.int32).view(n, B))
+    """
+
+    def __init__(self, env, n, book=False, history=0):
         if int(n) != n or not 1 <= int(n) <= abi.MAX_BRANCHES:
             raise ValueError("VecEnv.branch: n must be an integer in 1 .. %d" % abi.MAX_BRANCHES)
+        self.history = int(history)
+        if int(history) != history or not 0 <= self.history <= abi.MAX_HISTORY:
+            raise ValueError("VecEnv.branch: history must be 0 or 1 .. %d" % abi.MAX_HISTORY)
         self.env, self.n = env, int(n)
         N, B, V, dev = self.n, env.B, env.V, env.device
         self.obs = torch.zeros((N, B, V), dtype=torch.float32, device=dev)
@@ -394,7 +426,33 @@ class Branches:
         self.terminal = torch.zeros((N, B), dtype=torch.uint8, device=dev)
         self.stepped = torch.zeros((N, B), dtype=torch.int32, device=dev)
         self.out = abi.BranchOut(self.obs.data_ptr(), self.reward.data_ptr(), self.terminal.data_ptr(), self.stepped.data_ptr())
+        self.book_out = self.hist_out = None
+        D, T = env.eng.params.depth, env.eng.params.max_trades
+        if book:
+            self.levels = torch.zeros((N, B, 4, D), dtype=torch.float32, device=dev)
+            self.own = torch.zeros((N, B, abi.VEC_OWN_WORDS), dtype=torch.float32, device=dev)
+            self.time_ms = torch.zeros((N, B), dtype=torch.int64, device=dev)
+            self.book_out = abi.VecBookOut(self.levels.data_ptr(), self.own.data_ptr(), self.time_ms.data_ptr())
+        if self.history:
+            K = self.history
+            self.hist_levels = torch.zeros((N, B, K, 4, D), dtype=torch.float32, device=dev)
+            self.hist_trades = torch.zeros((N, B, K, 2, T), dtype=torch.float32, device=dev)
+            self.hist_time_ms = torch.zeros((N, B, K), dtype=torch.int32, device=dev)
+            self.hist_valid = torch.zeros((N, B), dtype=torch.int32, device=dev)
+            self.hist_rec = torch.zeros((N, B), dtype=torch.int32, device=dev)
+            self.hist_out = abi.VecHistOut(self.hist_levels.data_ptr(), self.hist_trades.data_ptr(), self.hist_time_ms.data_ptr(),
+                                           self.hist_valid.data_ptr(), self.hist_rec.data_ptr())
         self.fork()
+
+    def _observing(self, fn, *args):
+        fn(*args)
+        if self.book_out is not None:
+            self.env.eng.branch_book(self.book_out)   # (right behind it on the engine's stream: the branches as the call left them)
+        if self.hist_out is not None:
+            self.env.eng.branch_history(self.history, self.hist_out)
+
+    def _call(self, fn, *args, inputs=()):
+        self.env._on_engine(self._observing, fn, *args, inputs=inputs)
 
     def _words(self, t, who, what):
         if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or t.device != self.env.device
@@ -405,14 +463,14 @@ class Branches:
     def fork(self):
         """lob_branch_fork again: every branch becomes a copy of its book's present state.  Returns (obs, reward, terminal, stepped):
         the books' latest observation and terminal word in every plane, reward 0, stepped 0."""
-        self.env._on_engine(self.env.eng.branch_fork, self.n, self.out)
+        self._call(self.env.eng.branch_fork, self.n, self.out)
         return self.obs, self.reward, self.terminal, self.stepped
 
     def step(self, actions):
         """lob_branch_step: actions int32 [n, B] on the engine's device.  Returns (obs, reward, terminal, stepped), the persistent
         tensors: per branch what VecEnv.step would return had the books been in that branch's state."""
         self._words(actions, "step", "actions")
-        self.env._on_engine(self.env.eng.branch_step, actions.data_ptr(), self.out, inputs=(actions,))
+        self._call(self.env.eng.branch_step, actions.data_ptr(), self.out, inputs=(actions,))
         return self.obs, self.reward, self.terminal, self.stepped
 
     def select(self, parent):
@@ -420,7 +478,7 @@ class Branches:
         call (outside 0 .. n - 1: it keeps itself).  Returns (obs, terminal) of the new arrangement; .reward and .stepped keep the
         last step's values in the old arrangement."""
         self._words(parent, "select", "parent")
-        self.env._on_engine(self.env.eng.branch_select, parent.data_ptr(), self.out, inputs=(parent,))
+        self._call(self.env.eng.branch_select, parent.data_ptr(), self.out, inputs=(parent,))
         return self.obs, self.terminal
 
     def close(self):

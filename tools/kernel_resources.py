@@ -12,8 +12,8 @@ if "--csv" in sys.argv:
     i = sys.argv.index("--csv")
     csv_path = sys.argv[i + 1]
     del sys.argv[i:i + 2]
-# (the library's fifteen device translation units, rl_markets_amd/csrc/lob_launch.h, compiled side by side)
-units = ["lob_engine.hip", "lob_tu_env.hip", "lob_tu_prepass.hip", "lob_tu_learn.hip", "lob_tu_stats.hip", "lob_tu_steplog.hip", "lob_tu_vec.hip", "lob_tu_vecbook.hip", "lob_tu_vechist.hip", "lob_tu_snapshot.hip", "lob_tu_vecact.hip", "lob_tu_vecfeat.hip", "lob_tu_vecpeek.hip", "lob_tu_vecroll.hip", "lob_tu_branch.hip"]
+# (the library's sixteen device translation units, rl_markets_amd/csrc/lob_launch.h, compiled side by side)
+units = ["lob_engine.hip", "lob_tu_env.hip", "lob_tu_prepass.hip", "lob_tu_learn.hip", "lob_tu_stats.hip", "lob_tu_steplog.hip", "lob_tu_vec.hip", "lob_tu_vecbook.hip", "lob_tu_vechist.hip", "lob_tu_snapshot.hip", "lob_tu_vecact.hip", "lob_tu_vecfeat.hip", "lob_tu_vecpeek.hip", "lob_tu_vecroll.hip", "lob_tu_branch.hip", "lob_tu_branchobs.hip"]
 procs = [subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "--cuda-device-only", "-c",
                            "-Rpass-analysis=kernel-resource-usage", "-Wno-unused-value", "-o", "/dev/null", u] + sys.argv[1:],
                           cwd=CSRC, stderr=subprocess.PIPE, stdout=subprocess.PIPE, text=True) for u in units]
