@@ -27,7 +27,10 @@ crosses a tie first where the shadow has blown its nudge up a thousandfold).  te
 the CPU over the same cases: at most one case in ten of a sweep may end early.
 
 Every case shows from the engine which kernels it ran: Engine.launches (lob_debug_launches), lob_get_path_stats, the hit-list
-count of lob_debug_light."""
+count of lob_debug_light.
+
+The vector-env look-ahead family (lob_vec_peek, lob_vec_rollout, the branch calls) restates half of a step of its own
+(rl_markets_amd/csrc/lob_peek.h): tests/test_gpu_lookahead_edges.py takes it to the same edges of depth, trade slots and window."""
 import ctypes as C
 import os
 

@@ -36,10 +36,11 @@ N_EVENTS = 160
 class Run:
     """One engine, its main oracle, the device buffers and the action arrays the engine has seen (what a shadow replays)."""
 
-    def __init__(self, B, ending="dry", depth=5, seed=0, p=None, n_events=N_EVENTS, mem=1 << 16, reset=True):
+    def __init__(self, B, ending="dry", depth=5, seed=0, p=None, n_events=N_EVENTS, mem=1 << 16, reset=True, rec=None):
         self.p = p if p is not None else make_params(depth, 2, mem)
         self.B, self.V, self.D = B, self.p.n_vars, self.p.depth
-        self.rec = engine.gen_stream_host(gen(n_events, ending, self.p), self.p.depth, self.p.max_trades, 0, B)
+        # (`rec`: the caller's records [B][n][W] in place of the generator's stream)
+        self.rec = rec if rec is not None else engine.gen_stream_host(gen(n_events, ending, self.p), self.p.depth, self.p.max_trades, 0, B)
         self.eng = engine.Engine(self.p, B)
         self.eng.load_events(self.rec)
         self.orc = self.new_oracle()

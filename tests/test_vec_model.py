@@ -8,10 +8,13 @@
      for byte at every operation, whatever saves, look-aheads, forks, branch steps and refused calls stand in between;
   d. the refusal texts are the rows of tests/test_gpu_refusal_matrix.py;
   e. coverage of the default seeds: conditions on the INPUTS of tests/test_gpu_call_sequences.py (if one fails, change the generator's
-     weights, not the assertion), the variant axes, and the model's wall time per sequence, which bounds that test's CPU share."""
+     weights, not the assertion), the variant axes -- the edge shapes of a quarter of the seeds among them, and a checksum over the
+     operations of every other seed, which are what they were before that axis came -- and the model's wall time per sequence, which
+     bounds that test's CPU share."""
 import collections
 import os
 import time
+import zlib
 
 import numpy as np
 import pytest
@@ -22,7 +25,7 @@ from tests import test_gpu_refusal_matrix as matrix
 from tests import vec_model
 from tests.test_gpu_vec_env import gen, make_params
 from tests.test_oracle_days import make_days
-from tests.vec_sequences import NEVER_REFUSED, Sequence, Variant
+from tests.vec_sequences import EDGE_SEEDS, NEVER_REFUSED, Sequence, Variant
 
 N_SEEDS = 24
 REAL_MOVES = ("reset", "days_set", "days_select", "vec_step", "clear_inventory", "td_step", "eval_step", "td_begin", "td_end")
@@ -228,9 +231,37 @@ def test_variant_axes():
     for axis, values in (("B", (3, 65, 130)), ("depth", (5, 10)), ("trades", (2, 3)), ("normed", (False, True)), ("days", (False, True)),
                          ("ending", ("dry", "session")), ("env16_off", (False, True))):
         count = collections.Counter(getattr(v, axis) for v in vs)
-        assert set(count) == set(values) and min(count.values()) >= 4, (axis, dict(count))
+        assert min(count[x] for x in values) >= 4, (axis, dict(count))
+        assert set(count) == set(values) | ({"depth": {1, 7}, "trades": {1, 8}}.get(axis, set())), (axis, dict(count))
     assert abs(sum(v.env16_off for v in vs) - N_SEEDS / 3) <= 1, "LOB_ENV16_MAX=0 on a third of the seeds"
     assert sum(v.B == 130 and v.days for v in vs) >= 2 and sum(v.B == 130 and v.normed for v in vs) >= 2
+    # the edge axis: a quarter of the seeds, every edge value three times, every B, both env-step forms, with and without a day library
+    edge = [v for v in vs if v.edge]
+    assert [v.seed for v in edge] == list(EDGE_SEEDS) and len(edge) == N_SEEDS // 4
+    assert all(v.depth in (1, 7) and v.trades in (1, 8) for v in edge) and all(v.depth in (5, 10) and v.trades in (2, 3) for v in vs if not v.edge)
+    for axis, values in (("depth", (1, 7)), ("trades", (1, 8))):
+        count = collections.Counter(getattr(v, axis) for v in edge)
+        assert set(count) == set(values) and min(count.values()) >= 3, (axis, dict(count))
+    assert {(v.depth, v.trades) for v in edge} == {(1, 1), (1, 8), (7, 1), (7, 8)}
+    assert sum(v.long and v.params().lb_pnl == 101 for v in edge) >= 3 and all(v.long == (v.edge and v.normed) for v in vs) and all(v.params().lb_pnl == 3 for v in vs if v.normed and not v.edge)
+    assert {v.B for v in edge} == {3, 65, 130} and {v.env16_off for v in edge} == {False, True} and {v.days for v in edge} == {False, True}
+
+
+# label() and describe() of every operation of the seeds that run no edge shape, as they were before the edge axis came: crc32
+UNCHANGED = {0: 0xf87dea7e, 1: 0xa2cd509e, 2: 0x5b680231, 4: 0x4e8b6358, 5: 0x74a31d76, 7: 0x6025f4c4, 8: 0x16b205bf, 9: 0xbdf94c61,
+             10: 0x0d6677e3, 12: 0x8e0fcd1b, 13: 0xb7d6dd8d, 15: 0xe68b3881, 16: 0x77d0e7c6, 17: 0x87cd35fd, 18: 0x3a4ccb78, 20: 0xbd6ca96c,
+             21: 0x455a461b, 23: 0xd8eabd7b}
+
+
+def test_the_other_seeds_keep_their_variant_and_operations():
+    assert sorted(UNCHANGED) == [s for s in range(N_SEEDS) if s not in EDGE_SEEDS]
+    for seed, want in UNCHANGED.items():
+        seq = Sequence(seed)
+        for _ in seq:
+            pass
+        got = zlib.crc32(("%s\n%s" % (seq.v.label(), "\n".join(seq.log))).encode())
+        seq.m.close()
+        assert got == want, "seed %d (%s): %08x, recorded %08x" % (seed, seq.v.label(), got, want)
 
 
 def test_coverage_of_the_default_seeds():
@@ -240,8 +271,22 @@ def test_coverage_of_the_default_seeds():
         t0 = time.perf_counter()
         seq = Sequence(seed)
         n_ops = 0
+        # (the seeds with windows of 101 steps: the edge is reached, not only set -- full windows, and non-zero NORMED rewards to compare)
+        edge = {"a book with 101 completed steps": False, "non-zero reward of a real step": False, "non-zero reward of a look-ahead": False,
+                "non-zero reward of a branch step behind a select": False}
+        selected = False
         for i, kind, args, want in seq:
             n_ops += 1
+            if seq.v.long and not want.refused:
+                full = seq.m.was_reset and bool((seq.m.books()["total_ticks"] >= seq.v.lb_pnl).any())
+                edge["a book with 101 completed steps"] |= full
+                selected = (selected or kind == "select") and kind not in ("fork", "reset", "close")
+                if kind == "vec_step":
+                    edge["non-zero reward of a real step"] |= full and any((s["reward"] != 0.0).any() for s in want.out["steps"])
+                elif kind in ("peek", "rollout"):
+                    edge["non-zero reward of a look-ahead"] |= full and bool((want.out["reward"] != 0.0).any())
+                elif kind == "bstep":
+                    edge["non-zero reward of a branch step behind a select"] |= selected and bool((want.out["reward"] != 0.0).any())
             if want.refused:
                 refused[kind] += 1
                 seen["branch calls on a set voided by lob_reset"] += kind in ("bstep", "select") and seq.m.branch == "void" and not seq.m.half_open
@@ -259,6 +304,7 @@ def test_coverage_of_the_default_seeds():
         times.append(dt)
         episodes.append(seq.m.episode)
         assert 60 <= n_ops <= 90
+        assert not seq.v.long or all(edge.values()), "seed %d (%s): %s" % (seed, seq.v.label(), edge)
         assert 3 * seq.stats["all_over_ops"] <= n_ops, "seed %d spends %d of %d ops with every book over" % (seed, seq.stats["all_over_ops"], n_ops)
         print("seed %2d  %-44s %2d ops  %d episodes  model %.2f s" % (seed, seq.v.label(), n_ops, seq.m.episode, dt))
         seq.m.close()

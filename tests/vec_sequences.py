@@ -24,11 +24,20 @@ DAY_LENGTHS = (160, 100, 130)
 MEM = 1 << 14   # (private weights of 130 books: the learner is exact at any table size)
 # kinds the contract never refuses once a stream is loaded
 NEVER_REFUSED = ("reset", "close", "status")
+EDGE_SEEDS = tuple(s for s in range(24) if s % 8 in (3, 6))
+LONG_FACTOR, LONG_PROLOGUE = 4, 110   # the edge seeds with lb_pnl 101: streams of 400 .. 640 events (225 steps and more), 110 steps in front
+EDGE_VISIT = ("vec_step", "fork", "bstep", "select", "bstep", "peek", "rollout")
 
 
 class Variant:
     """The shapes of one sequence, derived from its seed: each value of each axis occurs in at least four of the 24 default seeds
-    (tests/test_vec_model.py asserts it)."""
+    (tests/test_vec_model.py asserts it).  A quarter of the seeds (EDGE_SEEDS, seed % 8 in {3, 6}) run an edge shape in place of
+    their depth, trade slots and window: depth 1 or 7, one or eight trade slots, and lb_pnl 101 where the seed's reward is NORMED
+    -- the edges of tests/test_gpu_lookahead_edges.py under an order nobody chose.  A window of 101 steps never fills in an episode
+    of 160 events, so the seeds that have it (`long`) play streams four times as long, and every episode of theirs opens with EDGE_VISIT:
+    LONG_PROLOGUE real steps, behind which the windows are full, then a fork, a branch step, a select, a branch step, a peek and a
+    roll-out, all with non-zero NORMED rewards to compare (tests/test_vec_model.py asserts that they occur).  Every other seed is
+    what it was."""
 
     def __init__(self, seed):
         self.seed = seed
@@ -37,25 +46,34 @@ class Variant:
         self.depth = (5, 10)[seed % 2]
         self.trades = (2, 3)[(seed // 2) % 2]                # the <true> and <false> forms of the look-ahead step
         self.normed = (seed // 4) % 2 == 1                   # REWARD_NORMED, lb_pnl 3: the private window ring
+        self.edge = seed % 8 in (3, 6)
+        self.lb_pnl = 3
+        if self.edge:
+            self.depth = (1, 7)[seed % 2]                    # rows of 28 and 124 bytes
+            self.trades = (1, 8)[(seed // 3) % 2]            # the <true> form with one slot, step_event<LOB_MAX_TRADES>
+            self.lb_pnl = 101                                # (read under NORMED only)
+        self.long = self.edge and self.normed
+        self.n_events = LONG_FACTOR * N_EVENTS if self.long else N_EVENTS
+        self.day_lengths = tuple(LONG_FACTOR * n for n in DAY_LENGTHS) if self.long else DAY_LENGTHS
         self.days = seed % 4 in (1, 2)                       # a day library of unequal days
         self.ending = "dry" if self.days else ("session", "dry")[(seed // 3 + seed) % 2]
 
     def label(self):
-        return "B=%d D=%d T=%d %s %s%s%s" % (self.B, self.depth, self.trades, "normed-3" if self.normed else "pnl", self.ending,
+        return "B=%d D=%d T=%d %s %s%s%s" % (self.B, self.depth, self.trades, "normed-%d" % self.lb_pnl if self.normed else "pnl", self.ending,
                                              " days" if self.days else "", " env16-off" if self.env16_off else "")
 
     def params(self):
         p = make_params(self.depth, self.trades, MEM)
         if self.normed:
-            p.reward_measure, p.lb_pnl = abi.REWARD_NORMED, 3
+            p.reward_measure, p.lb_pnl = abi.REWARD_NORMED, self.lb_pnl
         return p
 
     def data(self):
         """(records [B][n][W] or None, days or None)"""
         p = self.params()
         if self.days:
-            return None, make_days(DAY_LENGTHS, first_id=2000 + self.seed, depth=self.depth, trades=self.trades)
-        return engine.gen_stream_host(gen(N_EVENTS, self.ending, p), self.depth, self.trades, 0, self.B), None
+            return None, make_days(self.day_lengths, first_id=2000 + self.seed, depth=self.depth, trades=self.trades)
+        return engine.gen_stream_host(gen(self.n_events, self.ending, p), self.depth, self.trades, 0, self.B), None
 
     def model(self):
         rec, days = self.data()
@@ -86,6 +104,7 @@ class Sequence:
         self.refusing = False
         self.void_probe = 0
         self.stats = {"all_over_ops": 0}
+        self.visit = []                 # what is left of EDGE_VISIT in this episode (Variant.long)
 
     # ---- arguments ------------------------------------------------------------------------------------------------------------------
     def actions(self, shape, p_hole=0.06):
@@ -271,6 +290,10 @@ class Sequence:
                 k = "days_set" if r.random() < 0.5 else "days_select"
                 return k, self.args_of(k)
             return "reset", {}
+        if self.v.long and self.ops_since_reset == 0 and not m.half_open:
+            self.visit = list(EDGE_VISIT)
+        if self.visit and not m.half_open:
+            return self.visit_one(self.visit.pop(0))
         if m.half_open:
             if i >= self.length - 1:
                 return "td_end", {}   # (a sequence ends on a whole step: the last sweep compares the books)
@@ -293,6 +316,21 @@ class Sequence:
         if kind == "td_begin":
             self.half_refusals = 0
         return kind, self.args_of(kind)
+
+    def visit_one(self, kind):
+        """The next call of EDGE_VISIT, with arguments that keep every book stepping."""
+        m, r = self.m, self.rng
+        if kind == "vec_step":
+            return kind, {"actions": self.actions((LONG_PROLOGUE, m.B), 0.0)}
+        if kind == "fork":
+            return kind, {"N": 2}
+        if kind == "bstep":
+            return kind, {"actions": self.actions((m.N, m.B), 0.0)}
+        if kind == "select":
+            return kind, {"parent": r.integers(0, m.N, size=(m.N, m.B)).astype(np.int32)}
+        if kind == "peek":
+            return kind, {"mask": abi.PEEK_ALL}
+        return kind, {"plans": self.actions((2, 4, m.B), 0.0), "gamma": 1.0}
 
     def refused_one(self):
         """The refusable calls take turns by kind, so that every kind is refused across a handful of seeds."""
