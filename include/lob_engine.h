@@ -623,7 +623,7 @@ int lob_vec_update(lob_engine* e, const float* dev_vars, int32_t n, const int32_
  * synchronisation.  Allowed after lob_snapshot_restore (it reads the environment only).  LOB_EINVAL, with a message naming the call:
  * a NULL engine or out, action_mask 0 or with a bit at or above LOB_N_ACTIONS.  LOB_ESTATE: before the first lob_reset, between
  * lob_td_step_begin and lob_td_step_end, and on a stream whose market track is a ring (longer than LOB_TRACK_RING events: the
- * snapshot calls are refused there too).  All four members NULL: LOB_OK, nothing is launched. */
+ * snapshot calls are refused there too) unless lob_look_ring is on.  All four members NULL: LOB_OK, nothing is launched. */
 #define LOB_PEEK_ALL 0x1FFu
 typedef struct lob_vec_peek_out {   /* DEVICE pointers on the engine's GPU; any may be NULL = not wanted; action-major planes */
     float*   obs;                   /* [9][n_books][n_vars] */
@@ -662,7 +662,7 @@ int lob_vec_peek(lob_engine* e, uint32_t action_mask, const lob_vec_peek_out* ou
  *   Allowed after lob_snapshot_restore and while the step log records.  Refusals carry a message naming the call, and a refused call
  * writes nothing.  LOB_EINVAL: a NULL engine, out or dev_actions; n_plans outside 1 .. LOB_MAX_ROLLOUT_PLANS; horizon outside
  * 1 .. LOB_MAX_ROLLOUT_STEPS; gamma NaN or outside [0, 1].  LOB_ESTATE: before the first lob_reset, between lob_td_step_begin and
- * lob_td_step_end, and on a stream whose market track is a ring (longer than LOB_TRACK_RING events).  LOB_ENOMEM: the workspace does
+ * lob_td_step_end, and on a stream whose market track is a ring (longer than LOB_TRACK_RING events) unless lob_look_ring is on.  LOB_ENOMEM: the workspace does
  * not fit.  All five members NULL: LOB_OK, nothing is launched. */
 #define LOB_MAX_ROLLOUT_PLANS 64
 #define LOB_MAX_ROLLOUT_STEPS 64
@@ -710,7 +710,7 @@ int lob_vec_rollout(lob_engine* e, const int32_t* dev_actions /* [P][H][B] */, i
  *   All work is enqueued on the engine's stream (lob_stream) and nothing is read back.  Allowed after lob_snapshot_restore and while
  * the step log records.  Refusals carry a message naming the call, and a refused call writes nothing.  LOB_EINVAL: a NULL engine; NULL
  * dev_actions or dev_parent; NULL out for lob_branch_step; n_branches outside 1 .. LOB_MAX_BRANCHES.  LOB_ESTATE: before the first
- * lob_reset, between lob_td_step_begin and lob_td_step_end, on a stream whose market track is a ring, and -- step and select -- with
+ * lob_reset, between lob_td_step_begin and lob_td_step_end, on a stream whose market track is a ring unless lob_look_ring is on, and -- step and select -- with
  * no live set.  LOB_ENOMEM: a buffer does not fit (the message gives its bytes).  All members NULL: fork and select still act on the
  * set and step still steps; nothing is written to the caller. */
 #define LOB_MAX_BRANCHES 64
@@ -744,12 +744,54 @@ int lob_branch_close (lob_engine* e);
  * synchronisation.  Nothing of the engine and nothing of the set changes.  Allowed after lob_snapshot_restore, while the step log
  * records and while the real books step on.  LOB_EINVAL: a NULL engine, a NULL out, K outside [1, LOB_MAX_HISTORY]; a struct whose
  * members are all NULL is LOB_OK and launches nothing.  LOB_ESTATE, with a message naming the call: before the first lob_reset,
- * between lob_td_step_begin and lob_td_step_end, on a stream whose market track is a ring (no set can be forked there), and with no
+ * between lob_td_step_begin and lob_td_step_end, on a stream whose market track is a ring unless lob_look_ring is on, and with no
  * live set -- never forked, voided by lob_reset, closed.  A refused call writes nothing.
  *   Not offered: the book and the window at the leaves of lob_vec_peek / lob_vec_rollout -- those launches keep no end state; a
  * leaf's book is a branch set stepped under the plan. */
 int lob_branch_book   (lob_engine* e, const lob_vec_book_out* out);
 int lob_branch_history(lob_engine* e, int32_t K, const lob_vec_hist_out* out);
+
+/* ---- look-aheads on a ring-mode stream: the switch and the window ---
+ * A stream of more than LOB_TRACK_RING events keeps only the latest entries of its market track, as a ring that the step calls
+ * refill every LOB_TRACK_REFILL steps.  lob_vec_peek, lob_vec_rollout, lob_branch_* and lob_branch_book / lob_branch_history are
+ * refused there (LOB_ESTATE) UNLESS the caller has switched them on, per engine, because on a ring they have two outcomes that a
+ * resident track cannot produce and a caller must know of.
+ *   lob_look_ring(e, on): a host flag, off after lob_create, kept across lob_reset; LOB_ESTATE between lob_td_step_begin and
+ * lob_td_step_end, LOB_EINVAL for a NULL engine.  While it is on, the calls named above run on a ring track.  The snapshot calls stay
+ * refused there: they need entries BEHIND the cursor, which are gone.  On a resident track the flag changes nothing at all.
+ *   THE WINDOW.  Per book, the pre-pass has written n_track entries so far (all of the stream once `complete`), and the ring holds
+ * the latest of them.  With hi = n_track and lo = max(0, n_track - ring length + LOB_TRACK_WINDOW_MARGIN) the one rule is:
+ *     a private state at cursor k can be served while lo <= k; a private step is served when it never needs an entry >= hi while
+ *     complete == 0.
+ * lo carries the margin of LOB_TRACK_WINDOW_MARGIN (4) entries that every refill grants the real cursor, which therefore is always
+ * inside the window.  On a resident track lo = 0 and hi = n_track.
+ *   lob_track_window(e, lo, hi, complete): the three words of every book into HOST arrays [n_books], as they stand behind everything
+ * enqueued so far.  It waits for the stream (the second call of this interface that does, after lob_vec_status): for diagnostics and
+ * tests.  LOB_EINVAL for a NULL argument, LOB_ESTATE before the first lob_reset.
+ *   THE REFILL.  In front of its launch a look-ahead d steps deep makes the refill that would fall due within its depth (one launch
+ * on the engine's stream, decided on the host without a read; the schedule of the step calls starts again from there): d = 1 for
+ * lob_vec_peek and lob_branch_fork, d = horizon for lob_vec_rollout, d = 1 + lead for lob_branch_step, lead = the lob_branch_step
+ * calls since the set's last fork less the real steps since then, floored at 0.  A refill changes no bit that any call reports of the
+ * real books.  It can push a branch that LAGS behind the real books out of the window.
+ *   THE TWO OUTCOMES, per cell, in the `terminal` planes of the look-ahead calls only (never in lob_vec_step / lob_get_terminal):
+ *     LOB_TERMINAL_AHEAD   the step would have read an entry >= hi while complete == 0.  It is dropped: stepped 0, reward +0.0.
+ *                          lob_vec_peek: obs = the book's present state.  lob_vec_rollout: the plan ends at that step for that book --
+ *                          that step and all later ones reward +0.0, stepped / obs / ret as behind the last completed step.
+ *                          lob_branch_step: the branch's stored state is NOT written; the same call succeeds once the real books
+ *                          have moved the window on.
+ *     LOB_TERMINAL_BEHIND  lob_branch_step only: a live branch (its own terminal 0) whose cursor is < lo.  Nothing is attempted,
+ *                          whatever its action: state not written, stepped 0, reward +0.0, obs unchanged.  lob_branch_select copies
+ *                          whatever a branch holds; lob_branch_fork makes every branch live again; lob_branch_book /
+ *                          lob_branch_history read the records, which are resident, and report the state the branch holds.
+ * Neither outcome touches the engine's sticky error word.  lob_vec_status reads and clears, with its own word, the number of AHEAD
+ * and of BEHIND cells since the last lob_vec_status / lob_reset; lob_look_counts returns the two numbers that call read (host words,
+ * nothing is waited for; either pointer may be NULL). */
+#define LOB_TERMINAL_AHEAD  3
+#define LOB_TERMINAL_BEHIND 4
+#define LOB_TRACK_WINDOW_MARGIN 4
+int lob_look_ring   (lob_engine* e, int on);
+int lob_track_window(lob_engine* e, int32_t* lo, int32_t* hi, int32_t* complete);
+int lob_look_counts (lob_engine* e, int64_t* n_ahead, int64_t* n_behind);
 
 /* ---- episode statistics of the whole batch ---------------------------------
  * What the reference logs about ONE environment after an episode -- the `training_log` row of Runner::RunEpisode

@@ -215,6 +215,12 @@ class BranchOut(C.Structure):
     _fields_ = [("obs", C.c_void_p), ("reward", C.c_void_p), ("terminal", C.c_void_p), ("stepped", C.c_void_p)]
 
 
+# look-aheads on a ring-mode stream (lob_look_ring): the two codes that only their `terminal` planes hold (LOB_TERMINAL_AHEAD,
+# LOB_TERMINAL_BEHIND) and the margin of the window's lower end (LOB_TRACK_WINDOW_MARGIN)
+TERMINAL_AHEAD, TERMINAL_BEHIND = 3, 4
+TRACK_WINDOW_MARGIN = 4
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LOB_ENGINE_LIB: an experiment build of the same library (tools/exp_prof.py, tools/exp_variants.sh)
 LIB_PATH = os.environ.get("LOB_ENGINE_LIB") or os.path.join(_HERE, "csrc", "liblob_engine.so")
@@ -298,6 +304,9 @@ def load():
         "lob_branch_close": (C.c_int, [vp]),
         "lob_branch_book": (C.c_int, [vp, P(VecBookOut)]),
         "lob_branch_history": (C.c_int, [vp, C.c_int32, P(VecHistOut)]),
+        "lob_look_ring": (C.c_int, [vp, C.c_int]),
+        "lob_track_window": (C.c_int, [vp, vp, vp, vp]),
+        "lob_look_counts": (C.c_int, [vp, P(C.c_int64), P(C.c_int64)]),
         "lob_snapshot_save": (C.c_int, [vp, C.c_int32, C.c_void_p]),
         "lob_snapshot_restore": (C.c_int, [vp, C.c_int32, C.c_void_p]),
         "lob_snapshot_free": (C.c_int, [vp, C.c_int32]),

@@ -208,7 +208,18 @@ void launch_env(lob_engine* e, hipStream_t st, const i32* actions, int count_upd
 }
 // Long streams: let the pre-pass run on every `track_refill` steps (lob_kernels.h prepass_extend_kernel)
 void maybe_refill_track(lob_engine* e) {
+    e->real_steps++;
     if (!e->chunked || ++e->steps_since_fill < e->sw.track_refill) return;
+    e->steps_since_fill = 0;
+    TimedLaunch t(e, "prepass_extend_kernel", nullptr, true);
+    lobk_prepass_extend(e->stream, e->P.T <= 2, e->sw.prepass_roles, (const DevParams*)e->P_dev, e->S);
+}
+// In front of a look-ahead `depth` steps deep on a ring (lob_look_ring): the real step is safe because the ring is refilled every
+// `track_refill` steps; the look-ahead gets the same guarantee when the refill that would fall inside its depth is made now.  A refill
+// moves no observable bit of the real books -- the track is a function of the stream alone, and what it overwrites lies behind the real
+// cursor by the margin.  Decided on the host's counters: no read, no synchronisation.
+void look_refill_track(lob_engine* e, long long depth) {
+    if (!e->chunked || !e->look_ring || (long long)e->steps_since_fill + depth <= (long long)e->sw.track_refill) return;
     e->steps_since_fill = 0;
     TimedLaunch t(e, "prepass_extend_kernel", nullptr, true);
     lobk_prepass_extend(e->stream, e->P.T <= 2, e->sw.prepass_roles, (const DevParams*)e->P_dev, e->S);
@@ -245,7 +256,7 @@ int guard(lob_engine* e, const char* who, unsigned needs) {
     if ((needs & RESET) && !e->was_reset) why = ": call lob_reset first";
     else if ((needs & WHOLE_STEP) && e->half_open) why = ": a learner step is half done (lob_td_step_begin without lob_td_step_end)";
     else if ((needs & NOT_RESTORED) && e->restored) why = ": books were put back by lob_snapshot_restore in this episode; the learner runs again after the next lob_reset";
-    else if ((needs & NO_RING) && e->chunked) why = ": the market track of this stream is a ring (longer than LOB_TRACK_RING events)";
+    else if ((needs & NO_RING) && e->chunked && !e->look_ring) why = ": the market track of this stream is a ring (longer than LOB_TRACK_RING events)";
     else if ((needs & NO_RING_BACK) && e->chunked) why = ": the market track of this stream is a ring (longer than LOB_TRACK_RING events): entries before the cursor are gone, no earlier state can be served";
     if (!why) return LOB_OK;
     lob_set_error(std::string(who) + why);
@@ -525,9 +536,9 @@ int lob_create(const lob_params* p, int32_t n_books, int32_t device, lob_engine*
     alloc(&e->rnd_dev, 2048 + 64);
     S.nzd_terms = e->rnd_dev ? e->rnd_dev + 2048 + LOB_N_ACTIONS : nullptr;  // term[1][.], term[2][.] (filled below)
     alloc(&e->actions_dev, B); alloc(&e->P_dev, 1); alloc(&e->S_dev, 1);
-    alloc(&e->vec_bad, 1);
+    alloc(&e->vec_bad, 3);   // (+ the two look-ahead cell counts)
     alloc(&e->vec_upd_tag, 1);
-    if (rc == LOB_OK && hipMemsetAsync(e->vec_bad, 0, sizeof(u64), e->stream) != hipSuccess) rc = LOB_EHIP;
+    if (rc == LOB_OK && hipMemsetAsync(e->vec_bad, 0, 3 * sizeof(u64), e->stream) != hipSuccess) rc = LOB_EHIP;
     if (rc == LOB_OK) { S.self = e->S_dev; memset(&e->S_pushed, 0xff, sizeof(DevState)); }
     if (rc == LOB_OK) rc = push_params(e);
     if (rc != LOB_OK) { lob_destroy(e); return rc; }
@@ -680,7 +691,7 @@ int lob_reset(lob_engine* e) {
     HIPCHK(hipMemsetAsync(e->S.acc_list_n, 0, 2 * sizeof(i32), e->stream));
     HIPCHK(hipMemsetAsync(e->S.acc_pend, 0, (size_t)e->B, e->stream));
     if (e->S.dir_list_n) HIPCHK(hipMemsetAsync(e->S.dir_list_n, 0, 2 * sizeof(i32), e->stream));
-    HIPCHK(hipMemsetAsync(e->vec_bad, 0, sizeof(u64), e->stream));   // (lob_vec_step's count of bad actions starts again)
+    HIPCHK(hipMemsetAsync(e->vec_bad, 0, 3 * sizeof(u64), e->stream));   // (lob_vec_step's count of bad actions starts again, and the look-aheads' two)
     if (e->slog_n) {   // the step log holds the episode that starts here (its rows need no clearing: the counts say which exist)
         HIPCHK(hipMemsetAsync(e->slog_cnt, 0, 2 * (size_t)e->slog_n * sizeof(i32), e->stream));
         e->slog_armed = true;

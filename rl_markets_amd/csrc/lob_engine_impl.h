@@ -214,7 +214,14 @@ struct lob_engine {
     int branch_cur = 0;         // which of the two holds the set
     int branch_n = 0;           // branches of the live set
     bool branch_live = false;
-    u64* vec_bad = nullptr;     // lob_vec_step: actions out of range since the last lob_vec_status / lob_reset (one device word)
+    u64* vec_bad = nullptr;     // lob_vec_step: actions out of range since the last lob_vec_status / lob_reset (one device word); behind it
+                                // [1], [2]: the look-aheads' ahead / behind cells on a ring track (lob_launch.h PeekSrc::look_cnt)
+    // lob_look_ring: the look-aheads run on a ring track.  Host words only: the real steps of the engine's life
+    // (maybe_refill_track counts them), their count at the set's last fork and the lob_branch_step calls since -- the set's lead over
+    // the real books --, and what the last lob_vec_status read of the two cell counts (lob_look_counts)
+    bool look_ring = false;
+    long long real_steps = 0, branch_fork_real = 0, branch_steps = 0;
+    int64_t look_ahead_seen = 0, look_behind_seen = 0;
     i32* vec_upd_tag = nullptr; // lob_vec_update: the number of the last launch that wrote a weight (one device word; lob_launch.h VecFeatSrc)
     i32 vec_upd_launch = 0;     // ... and the number of the last launch (never 0 once used)
     uint32_t vec_terms[27] = {0};   // lob_vec_terms: the 27 action terms mod M, as uploaded behind the hash table
@@ -260,7 +267,8 @@ namespace lob {
 //   NOT_RESTORED no lob_snapshot_restore in this episode: the learner's memory of the books' last transition (the rl::State objects,
 //                the traces, the hit lists) then belongs to another trajectory, and the learner calls wait for the next lob_reset
 //   NO_RING      the market track is resident, not a ring (a stream of more than LOB_TRACK_RING events): the look-aheads read the
-//                entries ahead of the cursor, and that all of them are there between two refills has not been shown
+//                entries ahead of the cursor, and a ring has outcomes a resident track cannot produce ("beyond the window", "fell
+//                behind the window": DESIGN.md 7n) -- refused unless the caller has asked for them with lob_look_ring
 //   NO_RING_BACK ... the same for the snapshots, which need the entries before the cursor: those are gone (a longer message)
 enum : unsigned { RESET = 1, WHOLE_STEP = 2, NOT_RESTORED = 4, NO_RING = 8, NO_RING_BACK = 16 };
 int guard(lob_engine* e, const char* who, unsigned needs);   // (e == NULL: LOB_EINVAL, no message)
@@ -275,6 +283,7 @@ constexpr unsigned lob_branch_fork = RESET | WHOLE_STEP | NO_RING, lob_branch_st
 constexpr unsigned lob_branch_book = lob_branch_step, lob_branch_history = lob_branch_step;
 constexpr unsigned lob_vec_features = WHOLE_STEP, lob_vec_update = WHOLE_STEP;   // (+ RESET behind it when the rows are the books')
 constexpr unsigned lob_snapshot_save = RESET | WHOLE_STEP | NO_RING_BACK, lob_snapshot_restore = RESET | WHOLE_STEP | NO_RING_BACK;
+constexpr unsigned lob_track_window = RESET;
 constexpr unsigned lob_get_state = RESET, lob_get_reward = RESET, lob_get_terminal = RESET;
 constexpr unsigned lob_clear_inventory = RESET | WHOLE_STEP, lob_episode_stats = RESET | WHOLE_STEP;
 constexpr unsigned lob_step_log_enable = WHOLE_STEP, lob_step_log_counts = WHOLE_STEP, lob_step_log_read = WHOLE_STEP;
@@ -297,6 +306,7 @@ int finalize_episode(lob_engine* e);
 void launch_env(lob_engine* e, hipStream_t st, const i32* actions, int count_updates, int b0, int nb, int par);
 void launch_step_log(lob_engine* e);
 void maybe_refill_track(lob_engine* e);
+void look_refill_track(lob_engine* e, long long depth);   // the same in front of a look-ahead `depth` steps deep (lob_look_ring)
 void launch_memo(lob_engine* e, int par, int which, int reset_lpar = -1);
 void drain_timers(lob_engine* e);
 void free_days(lob_engine* e);       // lob_tu_host_streams.hip

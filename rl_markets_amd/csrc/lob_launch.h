@@ -231,9 +231,10 @@ struct PeekSrc {
     i32 n_act;             // actions in the mask
     uint8_t act[12];       // [n_act] the set bits of the mask, ascending
     lob_vec_peek_out out;  // obs [9][B][V], reward [9][B], terminal [9][B], stepped [9][B]; NULL: not wanted
+    u64* look_cnt;         // `ring` launches: the engine's words [0] ahead, [1] behind cells (lob_vec_status); last, so nothing above moves
 };
-// vec_peek_kernel<t2>: n_act * Bpad / 64 one-wave blocks; `t2` as lobk_env's
-void lobk_vec_peek(hipStream_t st, bool t2, const DevParams* Pd, const DevState& S, const PeekSrc& a);
+// vec_peek_kernel<t2, ring>: n_act * Bpad / 64 one-wave blocks; `t2` as lobk_env's; `ring`: the look-ahead over a ring track (lob_peek.h)
+void lobk_vec_peek(hipStream_t st, bool t2, bool ring, const DevParams* Pd, const DevState& S, const PeekSrc& a);
 
 // ---- lob_tu_vecroll.hip ----
 // What lob_vec_rollout (include/lob_engine.h) takes beyond the parameters and the state, which vec_rollout_kernel receives as
@@ -248,9 +249,10 @@ struct RolloutSrc {
     f64 gamma;
     f64* shadow;
     lob_vec_rollout_out out;
+    u64* look_cnt;         // `ring` launches: as PeekSrc's
 };
-// vec_rollout_kernel<t2>: n_plans * Bpad / 64 one-wave blocks; `t2` as lobk_env's
-void lobk_vec_rollout(hipStream_t st, bool t2, const DevParams* Pd, const DevState& S, const RolloutSrc& a);
+// vec_rollout_kernel<t2, ring>: n_plans * Bpad / 64 one-wave blocks; `t2`, `ring` as lobk_vec_peek's
+void lobk_vec_rollout(hipStream_t st, bool t2, bool ring, const DevParams* Pd, const DevState& S, const RolloutSrc& a);
 
 // ---- lob_tu_branch.hip ----
 // What lob_branch_fork / lob_branch_step / lob_branch_select (include/lob_engine.h) take beyond the parameters and the state, which
@@ -265,11 +267,12 @@ struct BranchSrc {
     i32 B, Bpad;           // books; B rounded up to a multiple of 64
     i32 n_branches;
     lob_branch_out out;    // obs [N][B][V], reward [N][B], terminal [N][B], stepped [N][B]; NULL: not wanted
+    u64* look_cnt;         // step, `ring` launches: as PeekSrc's
 };
 // branch_fork_kernel: Bpad / 64 one-wave blocks, a lane per book writing its N copies
 void lobk_branch_fork(hipStream_t st, const DevParams* Pd, const DevState& S, const BranchSrc& a);
-// branch_step_kernel<t2>: n_branches * Bpad / 64 one-wave blocks; `t2` as lobk_env's
-void lobk_branch_step(hipStream_t st, bool t2, const DevParams* Pd, const DevState& S, const BranchSrc& a);
+// branch_step_kernel<t2, ring>: n_branches * Bpad / 64 one-wave blocks; `t2`, `ring` as lobk_vec_peek's
+void lobk_branch_step(hipStream_t st, bool t2, bool ring, const DevParams* Pd, const DevState& S, const BranchSrc& a);
 // branch_select_kernel: n_branches * Bpad / 64 one-wave blocks
 void lobk_branch_select(hipStream_t st, const DevParams* Pd, const BranchSrc& a);
 

@@ -137,4 +137,30 @@ __device__ inline f64 look_step_finish(const EnvCtx& c, EnvR& e, const StepAgg& 
     return peek_reward(c, e, wu, wd);
 }
 
+// ---- the private step over a RING track (include/lob_engine.h lob_look_ring / lob_track_window) ----
+// The kernels' `RING` instantiations only; nothing above reads any of this.  A book's ring holds the entries [n_track - track_len,
+// n_track).  The window the look-ahead serves is [lo, hi): hi = n_track, lo = n_track - track_len + LOB_TRACK_MARGIN floored at 0 -- the
+// margin prepass_extend_kernel (lob_kernels.h) grants the real cursor, for the same reason: a step at cursor k reads the entries k - 1
+// (the quotes, state_track) and k .. .  BEHIND: a private cursor < lo; the step is not attempted.  AHEAD: the event loop ended with
+// status 2 while the pre-pass is not complete -- next_state's (lob_env.h) LOB_ERR_TRACK_UNDERRUN condition; the mutated state is dropped.
+#define LOB_LOOK_AHEAD LOB_TERMINAL_AHEAD     // (include/lob_engine.h)
+#define LOB_LOOK_BEHIND LOB_TERMINAL_BEHIND
+struct LookWin { int lo, hi, complete; };
+__device__ __forceinline__ LookWin look_window(const DevState& S, int b) {
+    const BookMeta& M = S.meta[b];
+    const int hi = M.n_track, lo = hi - S.track_len + LOB_TRACK_MARGIN;
+    return {lo > 0 ? lo : 0, hi, M.complete};
+}
+// step_prologue takes BookMeta's two words from the context when it holds them: the look-ahead hands it the true n_track and
+// complete = 1, so that next_state's out-of-data arm runs without raising LOB_ERR_TRACK_UNDERRUN in the ENGINE's error word -- that
+// bit voids the real run.  Every other condition the step reports stays reported.  The kernel tells the two ends of a status 2 apart
+// by LookWin::complete.  (An incomplete pre-pass has ex_first = ex_cur = ex_last = -1: that arm then reads no record.)
+__device__ __forceinline__ void look_ring_ctx(EnvCtx& c, const LookWin& w) { c.pre_n_track = w.hi; c.pre_complete = 1; }
+// The launch's cells of one kind, counted in the engine's word (lob_vec_status): every lane of the one-wave block calls this, outside
+// any divergent region; one atomic per block that has such a cell, none otherwise (vec_actions_kernel, lob_tu_vec.hip).
+__device__ __forceinline__ void look_count(u64* word, bool mine) {
+    const unsigned long long m = __ballot(mine);
+    if (m != 0 && threadIdx.x == 0) atomicAdd(word, (u64)__popcll(m));
+}
+
 #endif

@@ -150,7 +150,11 @@ __global__ void __launch_bounds__(LOB_LOOK_BLOCK) branch_select_kernel(const Dev
 // finds the entry a full window replaces, the lane's own pushes included.  Under every other reward nothing reads the windows: they
 // stay as forked.  The state goes back only on lanes that stepped or ran dry; the epilogue runs over registers, so no store reaches
 // the engine's windows.  EnvCtx keeps the real S and b: the track, the records, the meta.
-template <bool T2>
+//   RING (lob_look_ring on a ring track; lob_peek.h): a live branch whose cursor is below the window is BEHIND -- nothing
+// is attempted, whatever its action, terminal LOB_LOOK_BEHIND --, a step that would run past the ring's last entry while the pre-pass is
+// not complete is AHEAD -- terminal LOB_LOOK_AHEAD.  Either way the stored state is not written, so stepped 0, reward +0.0, obs as it
+// was; the cells are counted in a.look_cnt[0] / [1], and nothing is raised in the engine's error word.
+template <bool T2, bool RING>
 __global__ void __launch_bounds__(LOB_LOOK_BLOCK) branch_step_kernel(const DevParams* __restrict__ Pp, DevState S, BranchSrc a) {
     const DevParams& P = *Pp;  // parameters read through the scalar cache, never copied to scratch
     constexpr int TM = T2 ? 2 : LOB_MAX_TRADES;
@@ -163,18 +167,22 @@ __global__ void __launch_bounds__(LOB_LOOK_BLOCK) branch_step_kernel(const DevPa
     const int B = a.B, V = P.V;
     const BranchSet& set = a.set;
     const lob_branch_out& out = a.out;
+    bool ahead = false, behind = false;
     if (b < B) {
         const size_t lane = (size_t)n * (size_t)a.Bpad + (size_t)b;
         const size_t o = (size_t)n * (size_t)B + (size_t)b;
         const int action = a.index[o];
         EnvCtx c(P, S, b, &tick_lds);
+        LookWin w = {0, 0, 1};
+        if constexpr (RING) { w = look_window(S, b); look_ring_ctx(c, w); }
         EnvR& e = lds_env[threadIdx.x].e;
         br_env_load(set, lane, e);
         f64 reward = 0.0;
         int stepped = 0;
         bool have_obs = false;
         const int term = lob_terminal(P, e.done, e.time_ms);
-        if (term == 0 && action >= 0 && action < LOB_N_ACTIONS) {
+        if constexpr (RING) behind = term == 0 && e.k < w.lo;
+        if (term == 0 && action >= 0 && action < LOB_N_ACTIONS && !(RING && behind)) {
             const bool win = P.reward_measure == LOB_REWARD_NORMED;   // (the set holds the rings exactly then: lob_branch_fork)
             const RMPtrs ru = br_window(set, 0, S.pnl_ups.w), rd = br_window(set, 1, S.pnl_downs.w);
             RMReg wu = rm_zero(), wd = wu;
@@ -211,17 +219,19 @@ __global__ void __launch_bounds__(LOB_LOOK_BLOCK) branch_step_kernel(const DevPa
                 reward = peek_reward(c, e, wu, wd);
                 stepped = 1;
             }
-            br_env_store(set, lane, e);   // stepped, or ran dry: the mutated state
+            if (RING && st == 2 && !w.complete) ahead = true;   // (the branch stays where it was)
+            else br_env_store(set, lane, e);   // stepped, or ran dry: the mutated state
         }
         if (!have_obs && out.obs) {
             const f32* vf = br_arr<f32>(set, BR_OFF.obs) + lane * 16;
             for (int i = 0; i < V; i++) stage[threadIdx.x * V + i] = vf[i];
         }
         if (out.reward) out.reward[o] = reward;
-        if (out.terminal) out.terminal[o] = (uint8_t)lob_terminal(P, e.done, e.time_ms);
+        if (out.terminal) out.terminal[o] = (uint8_t)((RING && ahead) ? LOB_LOOK_AHEAD : (RING && behind) ? LOB_LOOK_BEHIND : lob_terminal(P, e.done, e.time_ms));
         if (out.stepped) out.stepped[o] = stepped;
     }
     if (out.obs) look_rows_out(stage, out.obs, n, 1, B, pl.first_b, V);   // (uniform)
+    if constexpr (RING) { look_count(a.look_cnt, ahead); look_count(a.look_cnt + 1, behind); }
 }
 
 void lobk_branch_fork(hipStream_t st, const DevParams* Pd, const DevState& S, const BranchSrc& a) {
@@ -230,8 +240,11 @@ void lobk_branch_fork(hipStream_t st, const DevParams* Pd, const DevState& S, co
 void lobk_branch_select(hipStream_t st, const DevParams* Pd, const BranchSrc& a) {
     hipLaunchKernelGGL(branch_select_kernel, dim3((unsigned)(a.n_branches * (a.Bpad / LOB_LOOK_BLOCK))), dim3(LOB_LOOK_BLOCK), 0, st, Pd, a);
 }
-void lobk_branch_step(hipStream_t st, bool t2, const DevParams* Pd, const DevState& S, const BranchSrc& a) {
+void lobk_branch_step(hipStream_t st, bool t2, bool ring, const DevParams* Pd, const DevState& S, const BranchSrc& a) {
     const dim3 grid((unsigned)(a.n_branches * (a.Bpad / LOB_LOOK_BLOCK))), block(LOB_LOOK_BLOCK);
-    if (t2) hipLaunchKernelGGL(branch_step_kernel<true>, grid, block, 0, st, Pd, S, a);
-    else hipLaunchKernelGGL(branch_step_kernel<false>, grid, block, 0, st, Pd, S, a);
+    if (ring) {
+        if (t2) hipLaunchKernelGGL((branch_step_kernel<true, true>), grid, block, 0, st, Pd, S, a);
+        else hipLaunchKernelGGL((branch_step_kernel<false, true>), grid, block, 0, st, Pd, S, a);
+    } else if (t2) hipLaunchKernelGGL((branch_step_kernel<true, false>), grid, block, 0, st, Pd, S, a);
+    else hipLaunchKernelGGL((branch_step_kernel<false, false>), grid, block, 0, st, Pd, S, a);
 }

@@ -81,16 +81,69 @@ int lob_vec_status(lob_engine* e, int64_t* n_bad_actions) {
     if (!e) { lob_set_error("lob_vec_status: NULL engine"); return LOB_EINVAL; }
     HIPCHK(hipSetDevice(e->device));
     i32 flag = 0;
-    u64 bad = 0;
+    u64 words[3] = {0, 0, 0};   // actions out of range; the look-aheads' ahead and behind cells (lob_look_counts)
     HIPCHK(hipMemcpyAsync(&flag, e->S.error_flag, sizeof flag, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(&bad, e->vec_bad, sizeof bad, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemsetAsync(e->vec_bad, 0, sizeof(u64), e->stream));
+    HIPCHK(hipMemcpyAsync(words, e->vec_bad, sizeof words, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemsetAsync(e->vec_bad, 0, sizeof words, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
+    const u64 bad = words[0];
+    e->look_ahead_seen = (int64_t)words[1];
+    e->look_behind_seen = (int64_t)words[2];
     if (n_bad_actions) *n_bad_actions = (int64_t)bad;
     if (flag) return device_error_rc(flag);
     if (bad) { lob_set_error("lob_vec_step: " + std::to_string(bad) + " action(s) out of range since the last lob_vec_status; those books were not stepped"); return LOB_EINVAL; }
     return LOB_OK;
 }
+
+// ---- look-aheads on a ring track (include/lob_engine.h lob_look_ring) ----
+static_assert(LOB_TRACK_WINDOW_MARGIN == LOB_TRACK_MARGIN, "the header states the margin of prepass_extend_kernel");
+
+// A host flag: guard() lets the NO_RING calls through on a chunked engine while it is set.  Survives lob_reset.
+int lob_look_ring(lob_engine* e, int on) {
+    if (!e) { lob_set_error("lob_look_ring: NULL engine"); return LOB_EINVAL; }
+    if (e->half_open) { lob_set_error("lob_look_ring: a learner step is half done (lob_td_step_begin without lob_td_step_end)"); return LOB_ESTATE; }
+    e->look_ring = on != 0;
+    return LOB_OK;
+}
+
+// The window of every book's track, from BookMeta as it stands behind everything enqueued so far: waits for the stream.
+int lob_track_window(lob_engine* e, int32_t* lo, int32_t* hi, int32_t* complete) {
+    if (!e || !lo || !hi || !complete) { lob_set_error("lob_track_window: NULL argument"); return LOB_EINVAL; }
+    LOB_GUARD(e, lob_track_window);
+    HIPCHK(hipSetDevice(e->device));
+    std::vector<BookMeta> meta((size_t)e->B);
+    HIPCHK(hipMemcpyAsync(meta.data(), e->S.meta, (size_t)e->B * sizeof(BookMeta), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (int b = 0; b < e->B; b++) {
+        const int n = meta[(size_t)b].n_track, first = e->chunked ? n - e->S.track_len + LOB_TRACK_MARGIN : 0;
+        lo[b] = first > 0 ? first : 0;
+        hi[b] = n;
+        complete[b] = meta[(size_t)b].complete;
+    }
+    return LOB_OK;
+}
+
+// (a diagnostic export, beside lob_debug_launches: the real books' cursors in the units of the window -- events, where lob_get_books
+// reports records -- into a host array [B]; waits for the stream)
+int lob_debug_track_cursor(lob_engine* e, int32_t* k) {
+    if (!e || !k) { lob_set_error("lob_debug_track_cursor: NULL argument"); return LOB_EINVAL; }
+    LOB_GUARD(e, lob_track_window);
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipMemcpyAsync(k, e->S.k, (size_t)e->B * sizeof(i32), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return LOB_OK;
+}
+
+// What the last lob_vec_status read of the two cell counts (host words: nothing is waited for here)
+int lob_look_counts(lob_engine* e, int64_t* n_ahead, int64_t* n_behind) {
+    if (!e) { lob_set_error("lob_look_counts: NULL engine"); return LOB_EINVAL; }
+    if (n_ahead) *n_ahead = e->look_ahead_seen;
+    if (n_behind) *n_behind = e->look_behind_seen;
+    return LOB_OK;
+}
+
+// `ring` of the look-ahead launches: the instantiation with the two window checks runs exactly where they can say anything
+static bool look_on_ring(const lob_engine* e) { return e->chunked && e->look_ring; }
 
 // The order book and the agent's own words of every book into the caller's device buffers (lob_tu_vecbook.hip vec_book_kernel): one
 // launch on the engine's stream, nothing read back, nothing changed.
@@ -165,8 +218,8 @@ int lob_vec_act(lob_engine* e, int32_t mode, const lob_vec_act_out* out) {
 // What lob_vec_step would write under each action of the mask, into the caller's device buffers (lob_tu_vecpeek.hip vec_peek_kernel;
 // DESIGN.md 7j): one launch on the engine's stream, nothing read back, nothing of the engine's state changed -- no step number, no
 // memo list, no step-log row, no refill of the track.  Not refused after lob_snapshot_restore: it reads the environment only.
-// Refused on a ring track, like the snapshots: the look-ahead reads the entries ahead of the cursor exactly as the step does, but
-// that they are all there between two refills whenever it is called has not been shown.
+// Refused on a ring track unless lob_look_ring is on; then the refill that would fall due within the look-ahead's one step is made
+// first (look_refill_track) and the kernel's ring instantiation runs.
 int lob_vec_peek(lob_engine* e, uint32_t action_mask, const lob_vec_peek_out* out) {
     if (!e || !out) { lob_set_error("lob_vec_peek: NULL argument"); return LOB_EINVAL; }
     if (action_mask == 0 || (action_mask & ~(uint32_t)LOB_PEEK_ALL)) {
@@ -182,9 +235,11 @@ int lob_vec_peek(lob_engine* e, uint32_t action_mask, const lob_vec_peek_out* ou
     for (int k = 0; k < LOB_N_ACTIONS; k++)
         if (action_mask >> k & 1u) a.act[a.n_act++] = (uint8_t)k;
     a.out = *out;
+    a.look_cnt = e->vec_bad + 1;
+    look_refill_track(e, 1);
     {
         TimedLaunch t(e, "vec_peek_kernel", nullptr, true);
-        lobk_vec_peek(e->stream, e->P.T <= 2, (const DevParams*)e->P_dev, e->S, a);
+        lobk_vec_peek(e->stream, e->P.T <= 2, look_on_ring(e), (const DevParams*)e->P_dev, e->S, a);
     }
     HIPCHK(hipGetLastError());
     return LOB_OK;
@@ -224,9 +279,11 @@ int lob_vec_rollout(lob_engine* e, const int32_t* dev_actions, int n_plans, int 
         }
         a.shadow = e->roll_ws.p;
     }
+    a.look_cnt = e->vec_bad + 1;
+    look_refill_track(e, horizon);
     {
         TimedLaunch t(e, "vec_rollout_kernel", nullptr, true);
-        lobk_vec_rollout(e->stream, e->P.T <= 2, (const DevParams*)e->P_dev, e->S, a);
+        lobk_vec_rollout(e->stream, e->P.T <= 2, look_on_ring(e), (const DevParams*)e->P_dev, e->S, a);
     }
     HIPCHK(hipGetLastError());
     return LOB_OK;
@@ -275,6 +332,7 @@ int lob_branch_fork(lob_engine* e, int n_branches, const lob_branch_out* out) {
     if (rc) return rc;
     BranchSrc a = branch_src(e, n_branches, e->branch_cur);
     if (out) a.out = *out;
+    look_refill_track(e, 1);
     {
         TimedLaunch t(e, "branch_fork_kernel", nullptr, true);
         lobk_branch_fork(e->stream, (const DevParams*)e->P_dev, e->S, a);
@@ -282,6 +340,8 @@ int lob_branch_fork(lob_engine* e, int n_branches, const lob_branch_out* out) {
     HIPCHK(hipGetLastError());
     e->branch_n = n_branches;
     e->branch_live = true;
+    e->branch_fork_real = e->real_steps;   // the set's lead over the real books starts at 0
+    e->branch_steps = 0;
     return LOB_OK;
 }
 
@@ -295,9 +355,16 @@ int lob_branch_step(lob_engine* e, const int32_t* dev_actions, const lob_branch_
     BranchSrc a = branch_src(e, e->branch_n, e->branch_cur);
     a.index = dev_actions;
     a.out = *out;
+    a.look_cnt = e->vec_bad + 1;
+    {
+        // the set's lead: its steps since the fork less the real books' since then; the step reaches one further
+        const long long lead = e->branch_steps - (e->real_steps - e->branch_fork_real);
+        look_refill_track(e, 1 + (lead > 0 ? lead : 0));
+    }
+    e->branch_steps++;
     {
         TimedLaunch t(e, "branch_step_kernel", nullptr, true);
-        lobk_branch_step(e->stream, e->P.T <= 2, (const DevParams*)e->P_dev, e->S, a);
+        lobk_branch_step(e->stream, e->P.T <= 2, look_on_ring(e), (const DevParams*)e->P_dev, e->S, a);
     }
     HIPCHK(hipGetLastError());
     return LOB_OK;

@@ -23,7 +23,10 @@
 //   A book that is over (lob_get_terminal != 0) does not step, as under vec_actions_kernel: stepped 0, reward +0.0, obs = slot 2 of
 // S.vars.  A step that runs dry: stepped 0, reward +0.0, terminal 2, obs = slot 2 (vec_observe_kernel behind env_kernel's `ok` false).
 //   The rows leave through LDS as in vec_rows_out (lob_tu_vec.hip): the block's rows are contiguous in the action's plane.
-template <bool T2>
+//   RING (lob_look_ring on a ring track; lob_peek.h): a step that would run past the ring's last entry while the
+// pre-pass is not complete is an AHEAD cell -- stepped 0, reward +0.0, obs = slot 2, terminal LOB_LOOK_AHEAD, counted in a.look_cnt[0]
+// -- and raises nothing in the engine's error word.  A peek starts at the real cursor: it is never behind.
+template <bool T2, bool RING>
 __global__ void __launch_bounds__(LOB_LOOK_BLOCK) vec_peek_kernel(const DevParams* __restrict__ Pp, DevState S, PeekSrc a) {
     const DevParams& P = *Pp;  // parameters read through the scalar cache, never copied to scratch
     constexpr int TM = T2 ? 2 : LOB_MAX_TRADES;
@@ -35,6 +38,7 @@ __global__ void __launch_bounds__(LOB_LOOK_BLOCK) vec_peek_kernel(const DevParam
     const int action = a.act[pl.plane];
     const int b = pl.b, B = a.B, V = P.V;
     const lob_vec_peek_out& out = a.out;
+    bool ahead = false;
     if (b < B) {
         const int k0 = S.k[b], rc0 = S.rec_cur[b];  // in flight together
         const i32 done0 = S.done[b], tm0 = S.time_ms[b];
@@ -43,6 +47,8 @@ __global__ void __launch_bounds__(LOB_LOOK_BLOCK) vec_peek_kernel(const DevParam
         f64 reward = 0.0;
         if (term == 0) {
             EnvCtx c(P, S, b, &tick_lds);
+            LookWin w = {0, 0, 1};
+            if constexpr (RING) { w = look_window(S, b); look_ring_ctx(c, w); }
             LookLoads L;   // requested before the bulk of the state, so that the round trips overlap
             look_step_loads<TM>(c, k0, rc0, L);
             EnvR& e = lds_env[threadIdx.x].e;
@@ -58,6 +64,9 @@ __global__ void __launch_bounds__(LOB_LOOK_BLOCK) vec_peek_kernel(const DevParam
                 reward = look_step_finish(c, e, g, wu, wd, out.obs != nullptr, stage, V);
             }
             term = lob_terminal(P, e.done, e.time_ms);
+            if constexpr (RING) {
+                if (!ok && !w.complete) { ahead = true; term = LOB_LOOK_AHEAD; }
+            }
         }
         if (!ok && out.obs) look_obs_slot2(S, b, &stage[threadIdx.x * V], V);
         const size_t o = (size_t)action * (size_t)B + (size_t)b;
@@ -66,10 +75,14 @@ __global__ void __launch_bounds__(LOB_LOOK_BLOCK) vec_peek_kernel(const DevParam
         if (out.stepped) out.stepped[o] = ok ? 1 : 0;
     }
     if (out.obs) look_rows_out(stage, out.obs, action, 1, B, pl.first_b, V);   // (uniform)
+    if constexpr (RING) look_count(a.look_cnt, ahead);
 }
 
-void lobk_vec_peek(hipStream_t st, bool t2, const DevParams* Pd, const DevState& S, const PeekSrc& a) {
+void lobk_vec_peek(hipStream_t st, bool t2, bool ring, const DevParams* Pd, const DevState& S, const PeekSrc& a) {
     const dim3 grid((unsigned)(a.n_act * (a.Bpad / LOB_LOOK_BLOCK))), block(LOB_LOOK_BLOCK);
-    if (t2) hipLaunchKernelGGL(vec_peek_kernel<true>, grid, block, 0, st, Pd, S, a);
-    else hipLaunchKernelGGL(vec_peek_kernel<false>, grid, block, 0, st, Pd, S, a);
+    if (ring) {
+        if (t2) hipLaunchKernelGGL((vec_peek_kernel<true, true>), grid, block, 0, st, Pd, S, a);
+        else hipLaunchKernelGGL((vec_peek_kernel<false, true>), grid, block, 0, st, Pd, S, a);
+    } else if (t2) hipLaunchKernelGGL((vec_peek_kernel<true, false>), grid, block, 0, st, Pd, S, a);
+    else hipLaunchKernelGGL((vec_peek_kernel<false, false>), grid, block, 0, st, Pd, S, a);
 }

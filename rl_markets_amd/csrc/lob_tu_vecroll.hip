@@ -40,7 +40,11 @@ __device__ inline void roll_rm_prep(const RMPtrs& r, int B, int b, RMReg& g, int
 // reward is +0.0 and the lane's LDS row keeps the obs of the last completed step -- slot 2 of S.vars when none has completed.  Actions
 // out of range are compared, never used, and not counted.
 //   The rows leave through LDS as in vec_rows_out (lob_tu_vec.hip): the block's rows are contiguous in the plan's plane.
-template <bool T2>
+//   RING (lob_look_ring on a ring track; lob_peek.h): a step that would run past the ring's last entry while the
+// pre-pass is not complete ends the plan for that book -- that step and all later ones reward +0.0, `stepped`, obs and ret as they
+// stand behind the last completed step, terminal LOB_LOOK_AHEAD, the cell counted in a.look_cnt[0] -- and raises nothing in the engine's
+// error word.  A roll-out starts at the real cursor: it is never behind.
+template <bool T2, bool RING>
 __global__ void __launch_bounds__(LOB_LOOK_BLOCK) vec_rollout_kernel(const DevParams* __restrict__ Pp, DevState S, RolloutSrc a) {
     const DevParams& P = *Pp;  // parameters read through the scalar cache, never copied to scratch
     constexpr int TM = T2 ? 2 : LOB_MAX_TRADES;
@@ -52,8 +56,11 @@ __global__ void __launch_bounds__(LOB_LOOK_BLOCK) vec_rollout_kernel(const DevPa
     const int p = pl.plane, b = pl.b;
     const int B = a.B, V = P.V, H = a.horizon;
     const lob_vec_rollout_out& out = a.out;
+    bool ahead = false;
     if (b < B) {
         EnvCtx c(P, S, b, &tick_lds);
+        LookWin w = {0, 0, 1};
+        if constexpr (RING) { w = look_window(S, b); look_ring_ctx(c, w); }
         EnvR& e = lds_env[threadIdx.x].e;
         env_load(S, b, e);
         // the two PnL windows: read by the LOB_REWARD_NORMED reward only, so only kept then
@@ -90,22 +97,35 @@ __global__ void __launch_bounds__(LOB_LOOK_BLOCK) vec_rollout_kernel(const DevPa
                     peek_push(c, e, wu, wd);
                     reward = look_step_finish(c, e, g, wu, wd, out.obs != nullptr, stage, V);
                     n_done++;
+                } else {
+                    if constexpr (RING) ahead = !w.complete;
                 }
             }
             if (out.reward) out.reward[((size_t)p * (size_t)H + (size_t)h) * (size_t)B + (size_t)b] = reward;
+            if constexpr (RING) {
+                // the plan ends here: the rewards behind it are +0.0, and acc + d * (+0.0) leaves acc (never -0.0) as it is
+                if (ahead) {
+                    if (out.reward) for (int h2 = h + 1; h2 < H; h2++) out.reward[((size_t)p * (size_t)H + (size_t)h2) * (size_t)B + (size_t)b] = 0.0;
+                    break;
+                }
+            }
             acc = __dadd_rn(acc, __dmul_rn(disc, reward));
             disc = __dmul_rn(disc, a.gamma);
         }
         const size_t o = (size_t)p * (size_t)B + (size_t)b;
-        if (out.terminal) out.terminal[o] = (uint8_t)lob_terminal(P, e.done, e.time_ms);
+        if (out.terminal) out.terminal[o] = (uint8_t)((RING && ahead) ? LOB_LOOK_AHEAD : lob_terminal(P, e.done, e.time_ms));
         if (out.stepped) out.stepped[o] = n_done;
         if (out.ret) out.ret[o] = acc;
     }
     if (out.obs) look_rows_out(stage, out.obs, p, 1, B, pl.first_b, V);   // (uniform)
+    if constexpr (RING) look_count(a.look_cnt, ahead);
 }
 
-void lobk_vec_rollout(hipStream_t st, bool t2, const DevParams* Pd, const DevState& S, const RolloutSrc& a) {
+void lobk_vec_rollout(hipStream_t st, bool t2, bool ring, const DevParams* Pd, const DevState& S, const RolloutSrc& a) {
     const dim3 grid((unsigned)(a.n_plans * (a.Bpad / LOB_LOOK_BLOCK))), block(LOB_LOOK_BLOCK);
-    if (t2) hipLaunchKernelGGL(vec_rollout_kernel<true>, grid, block, 0, st, Pd, S, a);
-    else hipLaunchKernelGGL(vec_rollout_kernel<false>, grid, block, 0, st, Pd, S, a);
+    if (ring) {
+        if (t2) hipLaunchKernelGGL((vec_rollout_kernel<true, true>), grid, block, 0, st, Pd, S, a);
+        else hipLaunchKernelGGL((vec_rollout_kernel<false, true>), grid, block, 0, st, Pd, S, a);
+    } else if (t2) hipLaunchKernelGGL((vec_rollout_kernel<true, false>), grid, block, 0, st, Pd, S, a);
+    else hipLaunchKernelGGL((vec_rollout_kernel<false, false>), grid, block, 0, st, Pd, S, a);
 }

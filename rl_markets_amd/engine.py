@@ -289,6 +289,26 @@ class Engine:
             self._check(rc)
         return rc, int(n.value)
 
+    def look_ring(self, on):
+        """lob_look_ring: the per-engine switch that lets vec_peek, vec_rollout and the branch calls run on a ring-mode stream (off
+        after creation, kept across reset()).  There their `terminal` planes may hold abi.TERMINAL_AHEAD (the step would read beyond
+        the track's window; dropped) and, for branch_step, abi.TERMINAL_BEHIND (the branch fell behind the window; nothing
+        attempted).  Changes nothing on a resident track; the snapshots stay refused on a ring."""
+        self._check(self.lib.lob_look_ring(self.h, 1 if on else 0))
+
+    def track_window(self):
+        """lob_track_window: (lo, hi, complete), int32 arrays [B] -- the entries [lo, hi) of every book's market track that a
+        look-ahead can be served from (hi = the entries written so far; complete: that is all of the stream).  Waits for the stream."""
+        lo, hi, comp = (np.empty(self.B, dtype=np.int32) for _ in range(3))
+        self._check(self.lib.lob_track_window(self.h, lo.ctypes.data, hi.ctypes.data, comp.ctypes.data))
+        return lo, hi, comp
+
+    def look_counts(self):
+        """lob_look_counts: (ahead, behind) cells of the look-aheads on a ring as the last vec_status() read and cleared them."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._check(self.lib.lob_look_counts(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     def vec_book(self, out):
         """lob_vec_book: the depth levels of every book, the agent's own sixteen words (abi.OWN_*) and the market time, written to
         the device buffers of `out` (abi.VecBookOut) -- every value what get_books() reports, as f32; enqueued on the engine's
@@ -340,7 +360,7 @@ class Engine:
         book been given that action now, into plane `action` of the device buffers of `out` (abi.VecPeekOut: obs f32 [9, B, V],
         reward f64 [9, B], terminal uint8 [9, B], stepped int32 [9, B]; 0 = not wanted) -- and nothing of the engine changes.  The
         planes of the other actions are not written.  One launch, enqueued on the engine's stream; works after snapshot_restore();
-        refused on a ring-mode stream."""
+        refused on a ring-mode stream unless look_ring(True)."""
         self._check(self.lib.lob_vec_peek(self.h, int(mask), C.byref(out)))
 
     def vec_rollout(self, actions_ptr, n_plans, horizon, gamma, out):
@@ -350,7 +370,7 @@ class Engine:
         step, stepped int32 [P, B] completed steps, ret f64 [P, B] the rewards discounted by `gamma` in [0, 1]; 0 = not wanted) --
         and nothing of the engine changes.  An action outside 0 .. 8 skips that step for that book and is not counted by
         vec_status.  One launch, enqueued on the engine's stream; works after snapshot_restore() and with the step log on; refused
-        on a ring-mode stream.  With reward_measure NORMED and 1 < lb_pnl < horizon the first call (and one that needs more than
+        on a ring-mode stream unless look_ring(True).  With reward_measure NORMED and 1 < lb_pnl < horizon the first call (and one that needs more than
         any before) allocates the engine's workspace, which synchronises the device."""
         self._check(self.lib.lob_vec_rollout(self.h, C.c_void_p(actions_ptr), int(n_plans), int(horizon), float(gamma), C.byref(out)))
 
@@ -360,7 +380,7 @@ class Engine:
         f64 [N, B], terminal uint8 [N, B], stepped int32 [N, B]; 0 = not wanted) receives the books' latest observation, their
         terminal word, reward 0 and stepped 0 in every plane.  Nothing of the engine changes.  Enqueued on the engine's stream; the
         first fork, and one that needs a larger set than any before, allocates, which synchronises the device.  Refused on a
-        ring-mode stream."""
+        ring-mode stream unless look_ring(True)."""
         self._check(self.lib.lob_branch_fork(self.h, int(n_branches), None if out is None else C.byref(out)))
 
     def branch_step(self, actions_ptr, out):
@@ -538,6 +558,14 @@ class Engine:
         self._check(fn(self.h, _ptr(c)))
         return {"env_step_kernel": int(c[0]), "env_step16_kernel": int(c[1]), "env_kernel_fused": int(c[2]),
                 "learn_q_pair_kernel": int(c[3]), "learn_q_lane_kernel": int(c[4]), "learn_q_fast_kernel": int(c[5])}
+
+    def track_cursor(self):
+        """lob_debug_track_cursor (a diagnostic export): every book's cursor in events, the unit of track_window() -- int32 [B].  Waits."""
+        k = np.zeros(self.B, np.int32)
+        fn = self.lib.lob_debug_track_cursor
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p]
+        self._check(fn(self.h, _ptr(k)))
+        return k
 
     def hint_stats(self):
         """lob_debug_hint (a diagnostic export): learner steps that read the learn kernels' hand-back count, and of those the steps

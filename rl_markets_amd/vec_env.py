@@ -64,13 +64,13 @@ stay exactly where they are.  One-step expectimax targets under the engine's own
     q = env.q_values(o.view(9 * B, V)).view(9, B, 9).max(-1).values
     target = r + gamma * q * (t == 0)
 
-Not available on a ring-mode stream.  A VecEnv that never calls peek() allocates and launches nothing for it.
+On a ring-mode stream only with VecEnv(..., ring_lookahead=True) (below).  A VecEnv that never calls peek() allocates and launches nothing for it.
 
 rollout(plans, gamma) is the same model several steps deep (lob_vec_rollout): the books rolled forward H steps under each of P
 candidate plans per book, int32 [P, H, B] (or [P, H]: the same plan for every book), in one launch -- the reward of every step, the
 observation and terminal behind the last, the steps that completed and the discounted return, as fresh tensors; the books stay
-exactly where they are.  An action of -1 skips that step for that book: plans of unequal length.  Not available on a ring-mode
-stream.  A VecEnv that never calls rollout() allocates and launches nothing for it.
+exactly where they are.  An action of -1 skips that step for that book: plans of unequal length.  On a ring-mode stream only with VecEnv(..., ring_lookahead=True) (below).
+A VecEnv that never calls rollout() allocates and launches nothing for it.
 
 branch(n) makes a branch set (lob_branch_fork): n private copies of every book's environment state that stay on the device between
 calls and can be stepped one step at a time with actions a torch policy produces from their observations -- closed loop, where peek()
@@ -117,8 +117,17 @@ torch network over the book and the window choosing the actions of a closed loop
         br.step(a)
         ret += gamma ** h * br.reward
 
-Not available on a ring-mode stream.  A VecEnv that never calls branch() allocates and launches nothing for it, and a branch set
+On a ring-mode stream only with VecEnv(..., ring_lookahead=True) (below).  A VecEnv that never calls branch() allocates and launches nothing for it, and a branch set
 without the two options allocates and launches nothing for them.
+
+VecEnv(eng, ..., ring_lookahead=True) switches peek(), rollout() and branch() on for a ring-mode stream (lob_look_ring; a stream of
+more than LOB_TRACK_RING events, every recorded day).  There a cell's `terminal` may hold two more codes: abi.TERMINAL_AHEAD (3) -- the
+step would have read beyond the window of the market track that is in memory; it is dropped (stepped 0, reward 0; a roll-out's plan ends
+there for that book; a branch keeps its state and can be stepped again once the real books have stepped on) -- and, for a branch that
+has been left far behind the real books, abi.TERMINAL_BEHIND (4): nothing is attempted until select() or fork() replaces it.  A
+look-ahead may enqueue the track's refill in front of its launch.  .status() counts such cells in .ahead_cells / .behind_cells, and
+.track_window() returns (lo, hi, complete), int32 numpy arrays [B]: the track entries [lo, hi) a look-ahead is served from (it waits).
+Without the flag nothing changes and nothing new is launched or allocated; on a resident track the flag changes nothing.
 
 step() reads the actions from the tensor's device memory and writes into five persistent tensors (lob_vec_step,
 include/lob_engine.h): no copy to or from the host and no synchronisation.  The engine runs on a stream of its own; it is made
@@ -132,8 +141,11 @@ from . import abi
 
 
 class VecEnv:
-    def __init__(self, eng, book=False, history=0):
+    def __init__(self, eng, book=False, history=0, ring_lookahead=False):
         self.eng = eng
+        self.ahead_cells = self.behind_cells = 0
+        if ring_lookahead:
+            eng.look_ring(True)
         self.B, self.V = eng.B, eng.V
         dev = torch.device("cuda", torch.cuda.current_device())
         self.device = dev
@@ -391,9 +403,15 @@ class VecEnv:
 
     def status(self):
         """lob_vec_status: waits once; LOB_OK, or LOB_EINVAL when actions were out of range since the last call (their number
-        is left in .bad_actions).  A malformed event stream raises engine.LobError (LOB_EDATA)."""
+        is left in .bad_actions).  A malformed event stream raises engine.LobError (LOB_EDATA).  .ahead_cells / .behind_cells: the
+        look-aheads' cells of abi.TERMINAL_AHEAD / abi.TERMINAL_BEHIND since the last call (ring_lookahead=True; else 0)."""
         rc, self.bad_actions = self.eng.vec_status()
+        self.ahead_cells, self.behind_cells = self.eng.look_counts()
         return rc
+
+    def track_window(self):
+        """lob_track_window: (lo, hi, complete), int32 numpy arrays [B].  Waits for the engine's stream: for diagnostics and tests."""
+        return self.eng.track_window()
 
 
 class Branches:
